@@ -21,8 +21,11 @@ equal WORLD_SIZE; a plain `python bench.py --gpus N` starts the N rank processes
 processes, before any GPU use) and exits with their status.  DRAGG_BENCH_BACKEND=gloo rehearses
 N ranks on fewer GPUs (ranks share devices round-robin).
 
-Also reported (rank 0): `roofline` of the solver kernel (algorithmic HBM bytes per launch
-over the launch time measured with HIP events on the launch stream), `cpu_baseline` (N = 1
+A plain run sets up, warms up, times the steps and prints the result line; `--dump-outputs DIR`
+also writes what the last timed step returned (dump_outputs).  Everything else is behind `--full`:
+the per-status counts of the timed solves, the launches' occupancy, `roofline` of the solver
+kernel (algorithmic HBM bytes per launch over the launch time measured with HIP events on the
+launch stream, recorded only then) and the VALU / LDS bounds from the committed profiles, `cpu_baseline` (N = 1
 only): the repo's CPU restatement of the reference solve (oracle/, HiGHS MILP in place of
 GLPK_MI) on this host's cores -- the committed >= 1,000-home-step run of the same workload
 (`bench.py --cpu-only`, profiles/*/cpu_baseline_*.json, labelled as committed) with this run's
@@ -94,6 +97,14 @@ def parse(argv=None):
                     help="skip the per-step history write (collected_data); a configs[2] run keeps it")
     ap.add_argument("--keep-crashing-homes", action="store_true",
                     help="keep battery homes whose t = 0 solve fails (the reference raises KeyError at t = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything beside the headline figure: the in-run CPU baseline "
+                         "sample and the committed one, the solver kernel's time per step (HIP events) and its "
+                         "rooflines, the occupancy of the launches, the per-status counts of the timed solves")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64, finite; absent "
+                         "hash fields are 0 with a float32 <name>_present mask beside them; "
+                         "per-home arrays on a fixed, seeded sample of homes where the whole would pass 64 MB)")
     return ap.parse_args(argv)
 
 
@@ -420,6 +431,56 @@ def bench_community(args):
     return homes, oat, ghi, tou
 
 
+DUMP_BYTES = 48 << 20        # --dump-outputs: the per-home arrays' share of the 64 MB a dump may take
+
+
+def dump_outputs(out_dir, agg, total_steps):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float64
+    <name>.npy files (rank 0's shard), so that two builds can be compared output for output:
+
+    * agg_sums [3]: the step's [agg_load, forecast_load, agg_cost] (collect_data / reduce_history);
+    * homes [K]: the global indices of the homes the per-home arrays cover -- every home of the shard,
+      or a fixed, seeded sample of them (sorted) where all of them would pass DUMP_BYTES;
+    * status [K], int_path [K]: the step's solve status and integer-path bits per home;
+    * vals [NVAL][K], fc [NFC][H][K]: the per-home hash after the step (the values and forecast fields
+      the next step and collected_data read);
+    * history_row [NVAL][K]: the step's row of the history (with the history kept);
+    * <name>_present (float32, for agg_sums, vals, fc, history_row): 1 where the entry holds a number, 0
+      where the hash holds none (NaN there: a key the home's type does not have, a failed solve) --
+      such entries are written as 0, so every file holds finite numbers only.
+    """
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    agg.drain()
+    torch.cuda.synchronize()
+    t = total_steps - 1
+    b = agg.batch
+    n = int(b.N)
+    # (a hash field: 8 B of value + 4 B of its `_present` entry)
+    per_home = 12 * (2 * b.vals.shape[0] + b.fc.shape[0] * b.fc.shape[1]) + 8 * 3
+    k = min(n, DUMP_BYTES // per_home)
+    pick = np.sort(np.random.default_rng(2024).choice(n, size=k, replace=False)) if k < n else np.arange(n)
+    idx = torch.as_tensor(pick, dtype=torch.long, device=b.vals.device)
+
+    def homes_of(x):
+        return x.index_select(x.dim() - 1, idx).to(torch.float64).cpu().numpy()
+    arrays = {"agg_sums": agg.agg_hist[t].cpu().numpy().astype(np.float64),
+              "homes": np.asarray(agg.index)[pick].astype(np.float64),
+              "status": homes_of(agg.status_hist[t]), "int_path": homes_of(agg.path_hist[t]),
+              "vals": homes_of(b.vals), "fc": homes_of(b.fc)}
+    if agg.hist is not None:
+        arrays["history_row"] = homes_of(agg.hist[t])
+    for name, a in arrays.items():
+        if name in ("agg_sums", "vals", "fc", "history_row"):
+            # every written number is finite: an absent field (NaN in the hash: a key the home's type
+            # does not have, a failed solve) is written as 0 and marked 0 in <name>_present (float32)
+            ok = np.isfinite(a)
+            np.save(os.path.join(out_dir, f"{name}_present.npy"), np.ascontiguousarray(ok.astype(np.float32)))
+            a = np.where(ok, a, 0.0)
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def spawn_ranks(args):
     """`bench.py --gpus N` without a launcher: start N rank processes of this same command, one per
     GPU (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set as torch.distributed.run sets them), wait
@@ -493,7 +554,7 @@ def main():
         out["workload"] = cpu_workload_key(n_total, Hh, dt, args.month, args.rl_price if rl else None)
         print(json.dumps(out))
         return
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(homes, env, *cpu_args)
 
     import torch
@@ -550,14 +611,18 @@ def main():
         if not rl:
             agg.reduce_history()
         barrier()
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+        # (--full: HIP events around every step's launches, the kernel time of the rooflines)
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+               for _ in range(args.steps if args.full else 0)]
         t0 = time.perf_counter()
         for k in range(args.steps):
-            evs[k][0].record(stream)            # rl: the action's rollout solves are timed with its step
+            if evs:
+                evs[k][0].record(stream)        # rl: the action's rollout solves are timed with its step
             if rl:
                 action(args.warmup + k)
             agg.run_iteration()
-            evs[k][1].record(stream)
+            if evs:
+                evs[k][1].record(stream)
             if rl:
                 agg.collect_data().tolist()         # the agent reads the community sums on the host
             else:
@@ -588,18 +653,24 @@ def main():
         e = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         torch.distributed.all_reduce(e, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(e.item())
-    kern_ms = sum(a.elapsed_time(b) for a, b in evs) / args.steps
-    # per-status counts of the timed steps over EVERY rank (one small all-reduce after timing)
-    st = agg.status_hist[args.warmup:total_steps]
-    from dragg_amd import _lib as L
-    names = L.STATUS_NAMES
-    counts = torch.stack([(st == i).sum() for i in range(len(names))]).to(torch.float64)
-    if world > 1:
-        torch.distributed.all_reduce(counts)
-    counts = counts.cpu().tolist()
-    # the timed solves' integer paths over every rank (int_path): approximate schedules (bits 0-11), the
-    # step-function DP (bit 15)
-    paths = agg.approx_counts(args.warmup, total_steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, agg, total_steps)
+    if args.full:
+        kern_ms = sum(a.elapsed_time(b) for a, b in evs) / args.steps
+        # per-status counts of the timed steps over EVERY rank (one small all-reduce after timing)
+        st = agg.status_hist[args.warmup:total_steps]
+        from dragg_amd import _lib as L
+        names = L.STATUS_NAMES
+        counts = torch.stack([(st == i).sum() for i in range(len(names))]).to(torch.float64)
+        if world > 1:
+            torch.distributed.all_reduce(counts)
+        counts = counts.cpu().tolist()
+        # the timed solves' integer paths over every rank (int_path): approximate schedules (bits 0-11), the
+        # step-function DP (bit 15)
+        paths = agg.approx_counts(args.warmup, total_steps)
+        stat_counts = {name: int(c) for name, c in zip(names, counts)}
+        success = stat_counts["optimal"] / max(1, sum(stat_counts.values()))
+        stat_counts.update(paths)
     # the homes every rank solved (strided shards: the rank's share of the community)
     per_rank = torch.tensor([agg.batch.N], dtype=torch.int64, device="cuda" if backend == "nccl" else "cpu")
     if world > 1:
@@ -609,10 +680,7 @@ def main():
         dist_world = torch.distributed.get_world_size()
     else:
         homes_per_rank, dist_world = [int(agg.batch.N)], 1
-    stat_counts = {name: int(c) for name, c in zip(names, counts)}
-    success = stat_counts["optimal"] / max(1, sum(stat_counts.values()))
-    stat_counts.update(paths)
-    solves = (agg.batch.N if shard else n_total) * args.steps * (1 + fh)
+    solves =(agg.batch.N if shard else n_total) * args.steps * (1 + fh)
     value = solves / elapsed
     if rank == 0:
         H = agg.batch.H
@@ -622,13 +690,6 @@ def main():
             workload = (f"{n_total} homes x {args.steps} RL reward-price actions ({args.rl_price} price), each "
                         f"{fh} rollout timestep(s) + the committed {60 // dt}-min step, H={H} ({Hh} h), month "
                         f"{args.month}, run_rl_agg, int_mode={args.int_mode}")
-        alg_bytes = bytes_per_launch(agg.batch, success) * (1 + fh)     # rl: per action (rollouts + commit)
-        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
-        key = traffic_key(n_total, H, dt, args.month, args.int_mode, world, args.workload, args.steps, args.warmup,
-                          args.rl_price if rl else None, fh, args.shard_of if shard else 0,
-                          ("max" if shard_times else slow_rank) if shard else None, steps_mode(agg))
-        pmc, traffic_src = measured_pmc(key)
-        traffic = pmc.get("bytes_per_step")
         out = {
             "metric": "home-MPC solves/sec (homes x steps)", "value": value, "unit": "solves/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -662,29 +723,39 @@ def main():
             "steps_mode": steps_mode(agg),
             "lag_from_step": getattr(agg, "lag_from", None),
             "sim_wall_s": elapsed,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
-                         "frac": achieved / 8000.0,
-                         "traffic": (traffic / (kern_ms * 1e-3) / 1e9) if traffic else None,
-                         "traffic_bytes_per_step": traffic, "traffic_source": traffic_src,
-                         "profile_key": key,
-                         "profiled_kernel_ms_per_step": pmc.get("kernel_ms_per_step"),
-                         "kernel": (f"mpc_direct_kernel (DM_FRONT + DM_BUCKET launches of a step)"
-                                    if args.int_mode == "round" else "mpc_home_kernel"),
-                         "kernel_ms": kern_ms,
-                         "algorithmic_bytes_per_step": alg_bytes,
-                         "unit_note": "one step = the hot launch + the second launch of one timestep; HIP events "
-                                      "on the launch stream around run_iteration (lag mode: the main pass; the "
-                                      "side stream's step-function DP runs beside it and is in the wall time)"},
-            "cpu_baseline": (headline_cpu_baseline(committed_cpu_baseline(cpu_workload_key(n_total, Hh, dt, args.month,
-                                                                                            args.rl_price if rl else None)), cpu)
-                             if rank == 0 else None),       # (world > 1: the committed run only)
-            "status_counts": stat_counts,
             # RL: the headline counts the rollout re-solves too; the committed steps alone:
             "committed_solves_per_s": n_total * args.steps / elapsed,
+            "full": bool(args.full),
         }
-        out.update(extra_rooflines(pmc, traffic_src))
-        out["occupancy"] = occupancy(agg.batch) | (
-            {"wave_cycle_shares": out.pop("wave_cycle_shares")} if "wave_cycle_shares" in out else {})
+        if args.full:
+            alg_bytes = bytes_per_launch(agg.batch, success) * (1 + fh)     # rl: per action (rollouts + commit)
+            achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+            key = traffic_key(n_total, H, dt, args.month, args.int_mode, world, args.workload, args.steps, args.warmup,
+                              args.rl_price if rl else None, fh, args.shard_of if shard else 0,
+                              ("max" if shard_times else slow_rank) if shard else None, steps_mode(agg))
+            pmc, traffic_src = measured_pmc(key)
+            traffic = pmc.get("bytes_per_step")
+            out["roofline"] = {
+                "bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
+                "frac": achieved / 8000.0,
+                "traffic": (traffic / (kern_ms * 1e-3) / 1e9) if traffic else None,
+                "traffic_bytes_per_step": traffic, "traffic_source": traffic_src,
+                "profile_key": key,
+                "profiled_kernel_ms_per_step": pmc.get("kernel_ms_per_step"),
+                "kernel": (f"mpc_direct_kernel (DM_FRONT + DM_BUCKET launches of a step)"
+                           if args.int_mode == "round" else "mpc_home_kernel"),
+                "kernel_ms": kern_ms,
+                "algorithmic_bytes_per_step": alg_bytes,
+                "unit_note": "one step = the hot launch + the second launch of one timestep; HIP events "
+                             "on the launch stream around run_iteration (lag mode: the main pass; the "
+                             "side stream's step-function DP runs beside it and is in the wall time)"}
+            # (world > 1: the committed run only)
+            out["cpu_baseline"] = headline_cpu_baseline(
+                committed_cpu_baseline(cpu_workload_key(n_total, Hh, dt, args.month, args.rl_price if rl else None)), cpu)
+            out["status_counts"] = stat_counts
+            out.update(extra_rooflines(pmc, traffic_src))
+            out["occupancy"] = occupancy(agg.batch) | (
+                {"wave_cycle_shares": out.pop("wave_cycle_shares")} if "wave_cycle_shares" in out else {})
         print(json.dumps(out))
     if world > 1:
         torch.distributed.destroy_process_group()

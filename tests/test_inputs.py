@@ -3,9 +3,8 @@ reference produced for every golden scenario (tests/golden/make_golden.py ran th
 reference's own Aggregator): the community of `create_homes`, the upsampled weather, the
 TOU window after `join_data`'s forward fill, the start index and the run mask's series.
 
-The inputs are the reference's own data files (NSRDB weather, water-draw profiles), read in
-place (DRAGG_REFERENCE_DATA, default /root/reference/dragg/data); they are not copied into
-this repository, so these CPU tests skip where that directory is absent."""
+The inputs are the reference's own data files (NSRDB weather, water-draw profiles), stored as
+gzipped fixtures under tests/golden/data (pandas reads them in place)."""
 import json
 import math
 import os
@@ -15,11 +14,9 @@ import pytest
 
 from tests import fixtures as F
 
-DATA = os.environ.get("DRAGG_REFERENCE_DATA", "/root/reference/dragg/data")
-NSRDB = os.path.join(DATA, "nsrdb.csv")
-DRAWS = os.path.join(DATA, "waterdraw_profiles.csv")
-needs_data = pytest.mark.skipif(not (os.path.exists(NSRDB) and os.path.exists(DRAWS)),
-                                reason="reference data files not present")
+DATA = os.path.join(F.GOLDEN, "data")
+NSRDB = os.path.join(DATA, "nsrdb.csv.gz")
+DRAWS = os.path.join(DATA, "waterdraw_profiles.csv.gz")
 
 
 def _cfg(params):
@@ -34,7 +31,6 @@ def _window(cfg):
     return start, end, hours, dt, int(math.ceil(hours * dt))
 
 
-@needs_data
 @pytest.mark.parametrize("name", F.scenarios())
 def test_create_homes_matches_reference(name):
     """Every parameter, water-draw list and name of the community, bit-exact."""
@@ -47,7 +43,6 @@ def test_create_homes_matches_reference(name):
     assert json.loads(json.dumps(homes)) == d["homes"]
 
 
-@needs_data
 @pytest.mark.parametrize("name", F.scenarios())
 def test_environment_matches_reference(name):
     """Weather rows per dt, the TOU list with its quirks, the start index and the run mask."""

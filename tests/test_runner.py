@@ -2,19 +2,21 @@
 
 CPU: the host side of a run configured like a golden scenario (config -> weather / TOU ->
 start index -> community -> all_homes file, run directory) against what the reference's own
-Aggregator produced; needs the reference's data files in place (skips otherwise).
+Aggregator produced, from the reference's data files (gzipped fixtures under tests/golden/data).
 GPU: a whole run on synthetic NSRDB-format weather and water-draw files (nothing from the
 reference is read): results.json layout, series lengths (the reference's
 check_baseline_vals rule), Summary sums, checkpoints, and identity with a DeviceAggregator
 driven directly."""
+import gzip
 import json
 import os
+import shutil
 
 import numpy as np
 import pytest
 
 from tests import fixtures as F
-from tests.test_inputs import DATA, needs_data, _cfg
+from tests.test_inputs import DATA, _cfg
 
 
 def _write_config(path, params):
@@ -22,7 +24,6 @@ def _write_config(path, params):
         f.write(F.config_text(params))
 
 
-@needs_data
 @pytest.mark.parametrize("name", ["c1_h24", "spring_dt1", "negprice_dt2"])
 def test_runner_host_side_matches_reference(tmp_path, name):
     from dragg_amd.runner import Aggregator
@@ -31,7 +32,8 @@ def test_runner_host_side_matches_reference(tmp_path, name):
     data.mkdir()
     _write_config(data / "config.toml", d["params"])
     for f in ("nsrdb.csv", "waterdraw_profiles.csv"):
-        os.symlink(os.path.join(DATA, f), data / f)
+        with gzip.open(os.path.join(DATA, f + ".gz"), "rb") as src, open(data / f, "wb") as dst:
+            shutil.copyfileobj(src, dst)
     a = Aggregator(data_dir=str(data), outputs_dir=str(tmp_path / "outputs"))
     assert a.num_timesteps == d["env"]["num_timesteps"]
     a.flush()

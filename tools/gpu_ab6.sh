@@ -19,7 +19,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   done
   for lib in "${order[@]}"; do
     if [ "$lib" = cur ]; then unset DRAGG_LIB; else export DRAGG_LIB=$PWD/abl/$lib.so; fi
-    timeout -k 10 ${AB_LIMIT:-240} python3 -u bench.py --cpu-seconds 0 ${ABARGS:---steps 20 --warmup 5} > $OUT/$lib.$r.out 2> $OUT/$lib.$r.err || { echo "AB_FAIL $lib"; tail -5 $OUT/$lib.$r.err; exit 1; }
+    timeout -k 10 ${AB_LIMIT:-240} python3 -u bench.py --full --cpu-seconds 0 ${ABARGS:---steps 20 --warmup 5} > $OUT/$lib.$r.out 2> $OUT/$lib.$r.err || { echo "AB_FAIL $lib"; tail -5 $OUT/$lib.$r.err; exit 1; }
     grep '^{' $OUT/$lib.$r.out | tail -1 > $OUT/$lib.$r.json
     python3 -c "
 import json; d=json.load(open('$OUT/$lib.$r.json')); print('$lib', $r, round(d['ms_per_step'],4), 'ms/step kern', round(d['roofline']['kernel_ms'],4), {k: v for k, v in d['status_counts'].items() if v and k != 'optimal'})"

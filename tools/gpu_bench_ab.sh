@@ -3,6 +3,7 @@
 # Extra bench arguments via BENCH_ARGS.
 set -o pipefail
 mkdir -p gpurun_out/ab
+BENCH_ARGS="--full $BENCH_ARGS"      # (the lines' status_counts)
 for r in 1 2; do
   for lib in "$@"; do
     DRAGG_LIB=$PWD/varlib/$lib.so timeout -k 10 200 python -u bench.py --cpu-seconds 0 --steps 48 $BENCH_ARGS > gpurun_out/ab/bench_$lib.log 2>&1 || { echo BENCH_FAIL $lib; tail -20 gpurun_out/ab/bench_$lib.log; exit 1; }

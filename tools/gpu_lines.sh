@@ -4,7 +4,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/${TAG:-lines}
 mkdir -p $OUT
-run() { name=$1; shift; timeout -k 10 400 python3 bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "$name failed"; tail -3 $OUT/$name.err; exit 1; }
+run() { name=$1; shift; timeout -k 10 400 python3 bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "$name failed"; tail -3 $OUT/$name.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('$OUT/$name.json')); r=d['roofline']; print('$name', round(d['value']/1e6,3), 'M/s', round(d['ms_per_step'],4), 'ms/step', 'kernel', round(r['kernel_ms'],4), 'frac', r['frac'], 'traffic', r['traffic'], 'valu', d.get('roofline_valu',{}).get('frac'), {k: v for k, v in d['status_counts'].items() if v and k != 'optimal'})"; }
 run driver --gpus 1 --steps 20 --warmup 5

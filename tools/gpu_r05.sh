@@ -42,7 +42,7 @@ args_of() {
 }
 run() { name=$1
   if [ "${name#gloo2}" != "$name" ]; then export DRAGG_BENCH_BACKEND=gloo; else unset DRAGG_BENCH_BACKEND; fi
-  timeout -k 10 ${LINE_LIMIT:-400} python3 bench.py $(args_of $name) > $OUT/$name.out 2> $OUT/$name.err || { echo "$name failed"; tail -5 $OUT/$name.err; exit 1; }
+  timeout -k 10 ${LINE_LIMIT:-400} python3 bench.py --full $(args_of $name) > $OUT/$name.out 2> $OUT/$name.err || { echo "$name failed"; tail -5 $OUT/$name.err; exit 1; }
   grep '^{' $OUT/$name.out | tail -1 > $OUT/$name.json
   python3 -c "
 import json; d=json.load(open('$OUT/$name.json')); print('$name', round(d['value']/1e6,3), 'M/s', round(d['ms_per_step'],4), 'ms/step', 'kern', round(d['roofline']['kernel_ms'],4), (d.get('shard_emulation') or {}).get('max_over_shards'), {k: v for k, v in d['status_counts'].items() if v and k != 'optimal'})"; }
