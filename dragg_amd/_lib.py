@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # DRAGG_LIB: an alternative build of the same library (kernel experiments); default in-tree
 LIB_PATH = os.environ.get("DRAGG_LIB") or os.path.join(HERE, "libdragg_mi355x.so")
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # enums (mirror include/dragg_mi355x.h)
 BASE, PV_ONLY, BATTERY_ONLY, PV_BATTERY = 0, 1, 2, 3
@@ -56,7 +56,7 @@ class Dims(ctypes.Structure):
                 ("dt", ctypes.c_int32), ("n_draw_hours", ctypes.c_int32), ("n_env", ctypes.c_int32),
                 ("n_rp", ctypes.c_int32), ("int_mode", ctypes.c_int32), ("max_iter", ctypes.c_int32),
                 ("check_every", ctypes.c_int32), ("discount", ctypes.c_double), ("flags", ctypes.c_int32),
-                ("reserved", ctypes.c_int32)]
+                ("n_groups", ctypes.c_int32)]
 
 
 class Problem(ctypes.Structure):
@@ -102,7 +102,8 @@ EXPORTS = ["dragg_mpc_abi_version", "dragg_mpc_strerror", "dragg_mpc_lds_bytes",
            "dragg_mpc_kernel_info_get", "dragg_mpc_step",
            "dragg_mpc_solve_explicit", "dragg_mpc_aggregate", "dragg_mpc_season_noise", "dragg_mpc_reload_knobs",
            "dragg_mpc_lag_reset", "dragg_mpc_step_main", "dragg_mpc_step_side", "dragg_mpc_aggregate_rows",
-           "dragg_mpc_side_workspace_bytes", "dragg_mpc_side_grid", "dragg_mpc_source_hash"]
+           "dragg_mpc_side_workspace_bytes", "dragg_mpc_side_grid", "dragg_mpc_source_hash",
+           "dragg_mpc_replicate", "dragg_mpc_aggregate_groups"]
 
 _LIB = None
 
@@ -161,6 +162,8 @@ def load(path=LIB_PATH):
         f.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Problem), ctypes.POINTER(Hash), ctypes.POINTER(Out),
                       ctypes.c_int32, ctypes.POINTER(Lag), c_dp]
     lib.dragg_mpc_aggregate_rows.argtypes = [ctypes.POINTER(Dims), c_dp, ctypes.c_int32, c_dp, c_dp]
+    lib.dragg_mpc_replicate.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Hash), ctypes.POINTER(Hash), c_dp]
+    lib.dragg_mpc_aggregate_groups.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Hash), c_dp, c_dp]
     if lib.dragg_mpc_abi_version() != ABI_VERSION:
         raise DraggError("ABI version mismatch between dragg_amd and libdragg_mi355x.so")
     if not os.environ.get("DRAGG_LIB"):

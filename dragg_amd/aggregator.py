@@ -50,10 +50,13 @@ class DeviceAggregator:
         self.device = dev
         # batch_cls is injectable only so the multi-rank glue can be exercised with gloo on
         # CPU (tests/test_distributed.py); the solver itself is MPCBatch (HIP, no fallback).
-        self.batch = batch_cls(self.homes, oat, ghi, tou, start_index, reward_price, int_mode=int_mode,
-                              seed=seed, home_offset=rank, home_stride=world, max_iter=max_iter, check_every=check_every,
-                              device=dev, template_home=homes[0] if homes else None,
+        self._batch_cls = batch_cls
+        self._batch_kw = dict(int_mode=int_mode, seed=seed, home_offset=rank, home_stride=world, max_iter=max_iter,
+                              check_every=check_every, device=dev, template_home=homes[0] if homes else None,
                               **({"exact": True} if exact else {}))
+        self.batch = batch_cls(self.homes, oat, ghi, tou, start_index, reward_price, **self._batch_kw)
+        self._sweep_batches = {}     # G -> the G-replica batch of sweep()
+        self.sweep_counts = None
         self.num_timesteps = num_timesteps
         self.timestep = 0
         n = self.batch.N
@@ -272,6 +275,67 @@ class DeviceAggregator:
             self.restore(snap)
         if self.world > 1:
             torch.distributed.all_reduce(out, group=self.group)
+        return out
+
+    # ------------------------------------------------------------------ price sweep
+    # G candidate reward prices against the live community at once: a grouped batch (dims.n_groups,
+    # include/dragg_mi355x.h) holds G replicas of this shard's homes, replica g solved under prices[g]
+    # with the base homes' season noise.  The live state is fanned out to the replicas by one kernel
+    # and never written: no snapshot, no restore.
+    def _sweep_batch(self, G):
+        rb = self._sweep_batches.get(G)
+        if rb is None:
+            rb = self._batch_cls(self.homes, None, None, None, 0, (0.0,), groups=G, **self._batch_kw)
+            self._sweep_batches[G] = rb
+        # the live batch's environment, as it is now (the same device tensors)
+        for k in ("oat", "ghi", "tou", "start_index"):
+            if hasattr(self.batch, k):
+                setattr(rb, k, getattr(self.batch, k))
+        if hasattr(self.batch, "dims"):
+            rb.dims.n_env = self.batch.dims.n_env
+        return rb
+
+    def sweep(self, prices, steps, noise_fn=None, src=0):
+        """The community's response to each of G candidate reward-price lists (`prices` [G][n], n == 1
+        or n >= H) over `steps` timesteps ahead, nothing committed: a device tensor [G][steps][agg_load,
+        forecast_load, agg_cost], row g bit-identical to `forecast(steps)` under prices[g], all-reduced
+        once over the ranks.  With more than one rank the prices are rank `src`'s (one broadcast).  The
+        live batch's vals, fc, reward price, timestep, histories and status rows are only read.
+        `noise_fn(t)`: the season draw [H][shard homes] of step t (default: the keyed stream).
+        `self.sweep_counts` then holds, per candidate, the solves of this sweep by int_path (the masks
+        of `approx_counts`): {"approx_solves": [G], "step_dp_solves": [G], "later_launch_solves": [G]},
+        summed over the sweep's steps and over the ranks.
+        Device memory: the replica batch is kept (one per G): dragg_mpc_workspace_bytes at G * n homes
+        plus its hash arrays (vals 19 x G n, fc G n x 15 x H fp64) and parameter rows -- at 10k homes,
+        H = 48 and G = 8 under a price list 15.4 GB of workspace and 0.47 GB of hash arrays
+        (profiles/r07/sweep/sweep_line.json)."""
+        self.drain()
+        P = torch.as_tensor(np.asarray(prices, dtype=float) if not torch.is_tensor(prices) else prices,
+                            dtype=torch.float64).to(self.device)
+        if P.dim() != 2 or P.shape[0] < 1:
+            raise ValueError(f"sweep takes prices [G][n], not {list(P.shape)}")
+        P = P.contiguous()
+        if self.world > 1:
+            torch.distributed.broadcast(P, src=src, group=self.group)
+        G, steps = int(P.shape[0]), int(steps)
+        rb = self._sweep_batch(G)
+        rb.set_reward_price(P)
+        rb.replicate_from(self.batch)
+        out = torch.zeros((G, steps, 3), dtype=torch.float64, device=self.device)
+        counts = torch.zeros((3, G), dtype=torch.int64, device=self.device)
+        for s in range(steps):
+            t = self.timestep + s
+            rb.step(t, noise=noise_fn(t) if noise_fn else None, hist=None)
+            out[:, s].copy_(rb.aggregate_groups())
+            if hasattr(rb, "int_path"):
+                p = rb.int_path.view(G, rb.int_path.numel() // G)
+                counts += torch.stack([((p & L.PATH_APPROX_MASK) != 0).sum(1), ((p & L.PATH_STEPS) != 0).sum(1),
+                                       ((p & L.PATH_SECOND) != 0).sum(1)])
+        if self.world > 1:
+            torch.distributed.all_reduce(out, group=self.group)
+            torch.distributed.all_reduce(counts, group=self.group)
+        a, s_, m = counts.cpu().tolist()
+        self.sweep_counts = {"approx_solves": a, "step_dp_solves": s_, "later_launch_solves": m}
         return out
 
     # ------------------------------------------------------------------ checkpoint / resume

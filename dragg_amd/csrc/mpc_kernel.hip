@@ -1269,7 +1269,11 @@ DEV void lag_finish(const KArgs& a, int home) {
 // (get_initial_conditions, water_draws, set_environmental_variables, the season draw).
 // Returns DRAGG_ST_ERR_MISSING where the reference raises KeyError, else -1.
 // --------------------------------------------------------------------------------------
-template <bool EXPLICIT>
+// PM, the prologue's mode (a template argument of every solve kernel; the host picks the instantiation, so
+// the kernels of an ordinary step carry no trace of the grouped indexing): the step's inputs from the
+// problem arrays, explicit per-home inputs (dragg_mpc_solve_explicit), or a step of a grouped batch
+constexpr int PM_STEP = 0, PM_EXPLICIT = 1, PM_GROUPED = 2;
+template <int PM>
 DEV int prologue(const KArgs& a, Home& h, const Lds& L, const Io& io, int lane, int nt, double* red) {
     const int home = io.home;
     const int N = a.d.n_homes;
@@ -1281,7 +1285,7 @@ DEV int prologue(const KArgs& a, Home& h, const Lds& L, const Io& io, int lane, 
     load_params(h, a.p.params, N, home);
     const int H = h.H;
     int status_pre = -1;
-    if (EXPLICIT) {
+    if (PM == PM_EXPLICIT) {
         h.t = a.ex.t[home];
         h.T0 = a.ex.T0[home]; h.Tw0 = a.ex.Tw0[home]; h.E0 = h.batt ? a.ex.E0[home] : 0.0;
         h.counter = a.ex.counter[home];
@@ -1302,6 +1306,18 @@ DEV int prologue(const KArgs& a, Home& h, const Lds& L, const Io& io, int lane, 
         const int nraw = lag * dt;
         const int base_hour = t / dt;
         const int s0 = a.p.start_index + t;
+        // a grouped batch (dims.n_groups = G > 1: G consecutive replicas of N / G base homes): the home
+        // reads its group's price row and draws its base home's noise.  Both are the same for the whole
+        // block: computed from the first lane's home so that they stay in scalar registers
+        const double* rpl = a.p.reward_price;
+        int nhome = home;
+        if (PM == PM_GROUPED) {
+            const unsigned hs = (unsigned)__builtin_amdgcn_readfirstlane(home);
+            const unsigned nb = (unsigned)N / (unsigned)a.d.n_groups;
+            const unsigned g = hs / nb;
+            rpl += (size_t)g * a.d.n_rp;
+            nhome = (int)(hs - g * nb);
+        }
         auto rawv = [&](int idx) -> double {                  // np.repeat(list, dt) / dt
             const int hh = base_hour + idx / dt - lag;
             const double v = (hh >= 0 && hh < a.d.n_draw_hours) ? a.p.draw_hourly[(size_t)hh * N + home] : 0.0;
@@ -1315,7 +1331,7 @@ DEV int prologue(const KArgs& a, Home& h, const Lds& L, const Io& io, int lane, 
             L.draw[i] = d;
             L.oat[i] = a.p.oat[s0 + i];
             L.ghi[i] = a.p.ghi[s0 + i];
-            const double rp = a.p.reward_price[a.d.n_rp == 1 ? 0 : (i < a.d.n_rp ? i : a.d.n_rp - 1)];
+            const double rp = rpl[a.d.n_rp == 1 ? 0 : (i < a.d.n_rp ? i : a.d.n_rp - 1)];
             L.price[i] = (i < H) ? rp + a.p.tou[s0 + i] : 0.0;
         }
         // season draw (mpc_calc.py:220-223, 303-309)
@@ -1325,7 +1341,7 @@ DEV int prologue(const KArgs& a, Home& h, const Lds& L, const Io& io, int lane, 
             if (a.noise) z = a.noise[(size_t)k * N + home];
             else {
                 double z0, z1;
-                normal_pair(a.p.seed, a.p.home_offset + home * max(a.p.home_stride, 1), t, k >> 1, &z0, &z1);
+                normal_pair(a.p.seed, a.p.home_offset + nhome * max(a.p.home_stride, 1), t, k >> 1, &z0, &z1);
                 z = (k & 1) ? z1 : z0;
             }
             mx = fmax(mx, a.p.oat[s0 + k + 1] + pow(1.1, (double)k) * z);
@@ -1383,7 +1399,7 @@ DEV void write_missing(const KArgs& a, int home) {
 // --------------------------------------------------------------------------------------
 // LP kernel (int_mode relax / round_lp): one workgroup (one wave) per home, ADMM + polish
 // --------------------------------------------------------------------------------------
-template <bool EXPLICIT>
+template <int PM>
 __global__ __launch_bounds__(64) void mpc_home_kernel(KArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int home = blockIdx.x;
@@ -1396,7 +1412,7 @@ __global__ __launch_bounds__(64) void mpc_home_kernel(KArgs a) {
     Io io{a.vals, a.fc, N, home};
     Prof pf;
     pf.start(a.out.cycles != nullptr);
-    if (prologue<EXPLICIT>(a, h, L, io, lane, WAVE, nullptr) == DRAGG_ST_ERR_MISSING) {
+    if (prologue<PM>(a, h, L, io, lane, WAVE, nullptr) == DRAGG_ST_ERR_MISSING) {
         if (lane == 0) write_missing(a, home);
         return;
     }
@@ -4302,7 +4318,7 @@ constexpr int BK_BEAM = (int)(1u << 31); // ... and that schedule is the beam pa
 // step-function DP and its capacity escape's schedule -- the step-function launch runs itself
 constexpr int BK_NEED = (int)(1u << 31);
 
-template <bool EXPLICIT, int MODE, int NW = 1, int ILP = 1>
+template <int PM, int MODE, int NW = 1, int ILP = 1>
 DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int first_chain, int eflags = 0) {
     constexpr bool SECOND = MODE == DM_BUCKET || MODE == DM_MID;   // the bucketed DP + an exact big-front pass
     constexpr int NT = NW * WAVE;
@@ -4324,7 +4340,7 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
     Io io{a.vals, a.fc, N, home};
     Prof pf;
     pf.start(a.out.cycles != nullptr);
-    if (prologue<EXPLICIT>(a, h, L, io, lane, NT, D.sc) == DRAGG_ST_ERR_MISSING) {
+    if (prologue<PM>(a, h, L, io, lane, NT, D.sc) == DRAGG_ST_ERR_MISSING) {
         if (lane == 0) {
             write_missing(a, home);
         }
@@ -4763,7 +4779,7 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
     lag_finish(a, home);
 }
 
-template <bool EXPLICIT, int MODE, int NW = 1, int ILP = 1>
+template <int PM, int MODE, int NW = 1, int ILP = 1>
 __global__ __launch_bounds__(WAVE * NW, MODE == DM_FRONT ? (ILP > 1 ? 2 : 3) : MODE == DM_NARROW ? 1 : 2) void mpc_direct_kernel(KArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     char* const ws = a.lws ? a.lws : reinterpret_cast<char*>(a.p.workspace);
@@ -4783,7 +4799,7 @@ __global__ __launch_bounds__(WAVE * NW, MODE == DM_FRONT ? (ILP > 1 ? 2 : 3) : M
             }
             if (c & LAG_SIDE) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // the side pass's rows
         }
-        solve_direct<EXPLICIT, MODE, NW, ILP>(a, home, smem, 0, 0);
+        solve_direct<PM, MODE, NW, ILP>(a, home, smem, 0, 0);
         return;
     }
     // persistent: block b solves listed home b first, then takes the next ones off a shared counter
@@ -4798,7 +4814,7 @@ __global__ __launch_bounds__(WAVE * NW, MODE == DM_FRONT ? (ILP > 1 ? 2 : 3) : M
     for (int j = blockIdx.x; j < cnt;) {
         const int e = list[j];                      // home | flags | deferred chain << 30
         const int home = e & HOME_MASK, chain = (e >> 30) & 1;
-        if (home < N) solve_direct<EXPLICIT, MODE, NW>(a, home, smem, blockIdx.x, chain, e & (BK_DONE | BK_OK | BK_BEAM));
+        if (home < N) solve_direct<PM, MODE, NW>(a, home, smem, blockIdx.x, chain, e & (BK_DONE | BK_OK | BK_BEAM));
         __syncthreads();
         if (threadIdx.x == 0) take = (int)gridDim.x + atomicAdd(list + N + 1, 1);
         __syncthreads();
@@ -4814,6 +4830,7 @@ constexpr int NT_CELL = 256;
 constexpr int CELL_BLOCKS = 1024;           // blocks of the cell kernel (4 per CU)
 constexpr int CELL_ROW = NCELL + 16;        // an LDS row of cell_rows (the pair minima take NCELL + 1)
 __host__ __device__ inline int cell_lds_bytes(int H) { return (front_layout(H).bytes + 15) / 16 * 16 + 2 * CELL_ROW * 4; }
+template <int PM>
 __global__ __launch_bounds__(NT_CELL, 4) void cell_kernel(KArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int N = a.d.n_homes, H = a.d.horizon;
@@ -4835,7 +4852,7 @@ __global__ __launch_bounds__(NT_CELL, 4) void cell_kernel(KArgs a) {
         Prof pf;
         pf.start(a.out.cycles != nullptr);
         __syncthreads();
-        if (prologue<false>(a, h, L, io, tid, NT_CELL, D.sc) == DRAGG_ST_ERR_MISSING) continue;
+        if (prologue<PM>(a, h, L, io, tid, NT_CELL, D.sc) == DRAGG_ST_ERR_MISSING) continue;
         derive(h);
         int changes = 0;
         for (int k = tid & (WAVE - 1); k < H; k += WAVE) changes += (k > 0 && D.price[k] != D.price[k - 1]) ? 1 : 0;
@@ -4901,11 +4918,14 @@ __global__ void lag_reset_kernel(int* clk, int N, int t) {
 // independent loads (a step's sums are a latency-bound 240 KB read at 10k homes), then a wave
 // reduction and a pass over the 16 wave partials
 constexpr int AGG_NT = 1024;
-DEV void agg_sums(const double* vals, int N, double* out3) {
+// (the homes summed are columns [off, off + N) of rows `stride` apart: a whole batch is (N, 0, N), group g
+// of a grouped batch (Nb * G, g * Nb, Nb) -- thread i takes homes off + i, off + i + AGG_NT, ... in either,
+// so a group's sums are those of a batch of its Nb homes, bit for bit)
+DEV void agg_sums(const double* vals, int stride, int off, int N, double* out3) {
     __shared__ double red[3][AGG_NT / WAVE];
-    const double* p0 = vals + (size_t)DRAGG_K_P_GRID * N;
-    const double* p1 = vals + (size_t)DRAGG_K_FORECAST_P_GRID * N;
-    const double* p2 = vals + (size_t)DRAGG_K_COST * N;
+    const double* p0 = vals + (size_t)DRAGG_K_P_GRID * stride + off;
+    const double* p1 = vals + (size_t)DRAGG_K_FORECAST_P_GRID * stride + off;
+    const double* p2 = vals + (size_t)DRAGG_K_COST * stride + off;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
     for (int i = threadIdx.x; i < N; i += AGG_NT) {   // NaN (absent field) propagates
         s0 += p0[i];
@@ -4923,21 +4943,64 @@ DEV void agg_sums(const double* vals, int N, double* out3) {
     }
 }
 __global__ __launch_bounds__(AGG_NT) void aggregate_kernel(const double* vals, int N, double* out3) {
-    agg_sums(vals, N, out3);
+    agg_sums(vals, N, 0, N, out3);
 }
 // the sums of many steps at once, from the history rows the steps wrote ([rows][NVAL][N]): block r
 // sums row r exactly as aggregate_kernel sums vals (the same code: bit-identical)
 __global__ __launch_bounds__(AGG_NT) void aggregate_rows_kernel(const double* rows, int N, double* out) {
-    agg_sums(rows + (size_t)blockIdx.x * DRAGG_NVAL * N, N, out + (size_t)blockIdx.x * 3);
+    agg_sums(rows + (size_t)blockIdx.x * DRAGG_NVAL * N, N, 0, N, out + (size_t)blockIdx.x * 3);
+}
+// a grouped batch's sums (vals [NVAL][G * Nb]): block g sums the Nb homes of group g exactly as
+// aggregate_kernel sums a batch of those Nb homes (the same code, lanes and order: bit-identical)
+__global__ __launch_bounds__(AGG_NT) void aggregate_groups_kernel(const double* vals, int N, int Nb, double* out) {
+    agg_sums(vals, N, (int)blockIdx.x * Nb, Nb, out + (size_t)blockIdx.x * 3);
 }
 
-__global__ void noise_kernel(int N, int H, uint64_t seed, int off, int stride, int t, double* out) {
+// Fan a base batch's hash arrays out to the G replicas of a grouped batch (dragg_mpc_replicate).  Both
+// arrays are a segment of `rows` rows of R doubles whose row r goes to rows r * G + g (g < G) of the
+// destination: vals is NVAL rows of Nb (dst [NVAL][G][Nb]), fc one row of Nb * NFC * H (dst
+// [G][Nb * NFC * H]).  A thread reads one unit of the source once and stores it G times, lanes on
+// consecutive units (coalesced both ways).  A unit is 16 bytes where every row offset is (R even, both
+// bases 16-byte aligned: then g * R is even for every g), else 8 bytes -- replica offsets g * Nb are
+// not 16-byte aligned in general, and an odd Nb leaves vals no wider access that is aligned in every
+// replica.  The bits move through integer registers: NaN payloads arrive as they are.
+struct RepSeg {
+    const double* src;
+    double* dst;
+    long long R;           // doubles per row
+    long long units;       // units of the whole segment (rows * R doubles / the unit's)
+    int rows;
+    int wide;              // 1: 16-byte units
+};
+template <typename T>
+DEV void rep_copy(const RepSeg& s, long long u, int G) {
+    const long long Ru = s.R / (long long)(sizeof(T) / 8);              // units per row
+    const long long r = s.rows == 1 ? 0 : u / Ru, i = u - r * Ru;
+    const T v = reinterpret_cast<const T*>(s.src)[u];
+    T* d = reinterpret_cast<T*>(s.dst) + r * G * Ru + i;
+    for (int g = 0; g < G; ++g, d += Ru) *d = v;
+}
+constexpr int REP_NT = 256;
+constexpr int REP_BLOCKS_MAX = 4096;        // (16 per CU: a grid-stride loop over the units past that)
+__global__ __launch_bounds__(REP_NT) void replicate_kernel(RepSeg a, RepSeg b, int G) {
+    const long long n = a.units + b.units;
+    for (long long e = (long long)blockIdx.x * REP_NT + threadIdx.x; e < n; e += (long long)gridDim.x * REP_NT) {
+        const bool first = e < a.units;
+        const RepSeg& s = first ? a : b;
+        const long long u = first ? e : e - a.units;
+        if (s.wide) rep_copy<uint4>(s, u, G);
+        else rep_copy<unsigned long long>(s, u, G);
+    }
+}
+
+// (nb: the base homes of a grouped batch, N otherwise: a replica draws its base home's stream)
+__global__ void noise_kernel(int N, int H, uint64_t seed, int off, int stride, int t, double* out, int nb) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int pairs = (H + 1) / 2;
     if (idx >= N * pairs) return;
     const int home = idx % N, pr = idx / N;
     double z0, z1;
-    normal_pair(seed, off + home * stride, t, pr, &z0, &z1);
+    normal_pair(seed, off + (home % nb) * stride, t, pr, &z0, &z1);
     out[(size_t)(2 * pr) * N + home] = z0;
     if (2 * pr + 1 < H) out[(size_t)(2 * pr + 1) * N + home] = z1;
 }
@@ -4962,6 +5025,7 @@ int check_dims(const dragg_mpc_dims* d) {
     if (d->n_homes > HOME_MASK) return DRAGG_E_ARG;                   // the deferred lists' home field
     if (d->int_mode < DRAGG_INT_ROUND || d->int_mode > DRAGG_INT_FAIL) return DRAGG_E_ARG;
     if (d->flags & ~DRAGG_FLAG_EXACT) return DRAGG_E_ARG;
+    if (d->n_groups < 0 || (d->n_groups > 1 && d->n_homes % d->n_groups != 0)) return DRAGG_E_ARG;
     if (direct_mode(d) && d->sub_steps > 15) return DRAGG_E_ARG;     // 4-bit duty in the DP record
     if (direct_mode(d) && !direct_fits(d->horizon)) return DRAGG_E_HORIZON;
     if (kernel_lds_bytes(d) > 160 * 1024 - 256) return DRAGG_E_HORIZON;
@@ -5049,7 +5113,7 @@ int hot_ilp(int dev, int N) {
 
 // blocks of the persistent mid launch: as many as the GPU holds at once at its LDS (<= MID_SLOTS_MAX),
 // cached per (device, LDS bytes): a batch with another horizon gets its own occupancy
-template <bool EXPLICIT>
+template <int PM>
 int mid_slots(int dev, int H, int S) {
     constexpr int NC = 8;
     static int cache_lds[MAX_DEV][NC] = {};
@@ -5059,7 +5123,7 @@ int mid_slots(int dev, int H, int S) {
         if (cache_lds[dev][i] == lds) return cache_slots[dev][i];
     hipDeviceProp_t prop{};
     int per_cu = 0;
-    const void* k = (const void*)mpc_direct_kernel<EXPLICIT, DM_MID, NW_MID>;
+    const void* k = (const void*)mpc_direct_kernel<PM, DM_MID, NW_MID>;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess ||
         hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, NW_MID * WAVE, (size_t)lds) != hipSuccess)
@@ -5070,14 +5134,14 @@ int mid_slots(int dev, int H, int S) {
     return slots;
 }
 
-template <bool EXPLICIT>
+template <int PM>
 int launch(const KArgs& a, hipStream_t s) {
     static int attr_dev[MAX_DEV][10] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return DRAGG_E_HIP;
     int* const attr = attr_dev[dev];
     const int N = a.d.n_homes;
-    if (!direct_mode(&a.d)) return launch_kernel(mpc_home_kernel<EXPLICIT>, attr[0], a, N, 64, kernel_lds_bytes(&a.d), s);
+    if (!direct_mode(&a.d)) return launch_kernel(mpc_home_kernel<PM>, attr[0], a, N, 64, kernel_lds_bytes(&a.d), s);
     if (N == 0) return DRAGG_OK;
     // the deferred list starts empty (its length word), then the hot launch, then the second
     char* const wsb = reinterpret_cast<char*>(a.p.workspace);
@@ -5096,27 +5160,27 @@ int launch(const KArgs& a, hipStream_t s) {
     const size_t lds = kernel_lds_bytes(&a.d);
     const int nw = hot_waves();
 
-    const int rc = nw == 4 ? launch_kernel(mpc_direct_kernel<EXPLICIT, DM_FRONT, 4>, attr[4], b, N, 4 * WAVE, lds, s)
-                 : nw == 2 ? launch_kernel(mpc_direct_kernel<EXPLICIT, DM_FRONT, 2>, attr[3], b, N, 2 * WAVE, lds, s)
-                 : hot_ilp(dev, N) == 2 ? launch_kernel(mpc_direct_kernel<EXPLICIT, DM_FRONT, 1, 2>, attr[8], b, N, WAVE, lds, s)
-                                        : launch_kernel(mpc_direct_kernel<EXPLICIT, DM_FRONT, 1>, attr[1], b, N, WAVE, lds, s);
+    const int rc = nw == 4 ? launch_kernel(mpc_direct_kernel<PM, DM_FRONT, 4>, attr[4], b, N, 4 * WAVE, lds, s)
+                 : nw == 2 ? launch_kernel(mpc_direct_kernel<PM, DM_FRONT, 2>, attr[3], b, N, 2 * WAVE, lds, s)
+                 : hot_ilp(dev, N) == 2 ? launch_kernel(mpc_direct_kernel<PM, DM_FRONT, 1, 2>, attr[8], b, N, WAVE, lds, s)
+                                        : launch_kernel(mpc_direct_kernel<PM, DM_FRONT, 1>, attr[1], b, N, WAVE, lds, s);
     if (rc) return rc;
     // RL prices possible (a reward-price list): the cell bound of the deferred homes' indoor-air chains
     if (a.d.n_rp > 1) {
-        const int rcc = launch_kernel(cell_kernel, attr[7], b, min(N, CELL_BLOCKS), NT_CELL,
+        const int rcc = launch_kernel(cell_kernel<PM == PM_GROUPED ? PM_GROUPED : PM_STEP>, attr[7], b, min(N, CELL_BLOCKS), NT_CELL,
                                       (size_t)cell_lds_bytes(a.d.horizon), s);
         if (rcc) return rcc;
     }
     // the deferred homes: the mid launch (fronts of 384 labels, many blocks), its overflows to the
     // big launch (2,048 labels, 2 blocks per CU), what no front DP can take to the step-function DP
-    const int rcm = launch_kernel(mpc_direct_kernel<EXPLICIT, DM_MID, NW_MID>, attr[6], b,
-                                  min(N, mid_slots<EXPLICIT>(dev, a.d.horizon, a.d.sub_steps)), NW_MID * WAVE,
+    const int rcm = launch_kernel(mpc_direct_kernel<PM, DM_MID, NW_MID>, attr[6], b,
+                                  min(N, mid_slots<PM>(dev, a.d.horizon, a.d.sub_steps)), NW_MID * WAVE,
                                   (size_t)mid_layout(a.d.horizon, a.d.sub_steps).bytes, s);
     if (rcm) return rcm;
-    const int rc2 = launch_kernel(mpc_direct_kernel<EXPLICIT, DM_BUCKET, NW_BIG>, attr[2], b, min(N, SECOND_SLOTS),
+    const int rc2 = launch_kernel(mpc_direct_kernel<PM, DM_BUCKET, NW_BIG>, attr[2], b, min(N, SECOND_SLOTS),
                                   NW_BIG * WAVE, (size_t)big_layout(a.d.horizon, a.d.sub_steps).bytes, s);
     if (rc2) return rc2;
-    const int rcn = launch_kernel(mpc_direct_kernel<EXPLICIT, DM_NARROW, NT_STEPS / WAVE>, attr[5], b, min(N, NARROW_SLOTS),
+    const int rcn = launch_kernel(mpc_direct_kernel<PM, DM_NARROW, NT_STEPS / WAVE>, attr[5], b, min(N, NARROW_SLOTS),
                                   NT_STEPS, (size_t)narrow_layout(a.d.horizon, a.d.sub_steps, b.narrow_lds).bytes, s);
     return rcn;
 }
@@ -5175,7 +5239,7 @@ int launch_lag(const KArgs& a, bool side, hipStream_t s) {
         int rc = hot_ilp(dev, N) == 2 ? launch_kernel(mpc_direct_kernel<false, DM_FRONT, 1, 2>, attr[8], b, N, WAVE, lds, s)
                                       : launch_kernel(mpc_direct_kernel<false, DM_FRONT, 1>, attr[1], b, N, WAVE, lds, s);
         if (!rc && a.d.n_rp > 1)
-            rc = launch_kernel(cell_kernel, attr[7], b, min(N, CELL_BLOCKS), NT_CELL, (size_t)cell_lds_bytes(H), s);
+            rc = launch_kernel(cell_kernel<PM_STEP>, attr[7], b, min(N, CELL_BLOCKS), NT_CELL, (size_t)cell_lds_bytes(H), s);
         if (!rc) rc = launch_kernel(mpc_direct_kernel<false, DM_MID, NW_MID>, attr[6], b,
                                     min(N, mid_slots<false>(dev, H, a.d.sub_steps)), NW_MID * WAVE,
                                     (size_t)mid_layout(H, a.d.sub_steps).bytes, s);
@@ -5197,7 +5261,7 @@ int launch_lag(const KArgs& a, bool side, hipStream_t s) {
     int rc = launch_kernel(side_front_kernel, attr[0], b, grid[0], WAVE, lds, s);
     b.hot_list = nullptr;
     if (!rc && a.d.n_rp > 1)
-        rc = launch_kernel(cell_kernel, attr[7], b, grid[1], NT_CELL, (size_t)cell_lds_bytes(H), s);
+        rc = launch_kernel(cell_kernel<PM_STEP>, attr[7], b, grid[1], NT_CELL, (size_t)cell_lds_bytes(H), s);
     if (!rc) rc = launch_kernel(mpc_direct_kernel<false, DM_MID, NW_MID>, attr[6], b, grid[1], NW_MID * WAVE,
                                 (size_t)mid_layout(H, a.d.sub_steps).bytes, s);
     if (!rc) rc = launch_kernel(mpc_direct_kernel<false, DM_BUCKET, NW_BIG>, attr[2], b, grid[2],
@@ -5270,7 +5334,8 @@ int dragg_mpc_step(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, dr
     KArgs a{};
     a.d = *dims; a.p = *prob; a.vals = hash->vals; a.fc = hash->fc; a.out = *out; a.noise = noise;
     a.t = timestep;
-    return launch<false>(a, (hipStream_t)stream);
+    // (a grouped batch runs the kernels instantiated with the grouped prologue: an ordinary step's are untouched)
+    return a.d.n_groups > 1 ? launch<PM_GROUPED>(a, (hipStream_t)stream) : launch<PM_STEP>(a, (hipStream_t)stream);
 }
 
 static int lag_args(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, dragg_mpc_hash* hash,
@@ -5278,6 +5343,7 @@ static int lag_args(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, d
     int rc = check_dims(dims);
     if (rc) return rc;
     if (!direct_mode(dims) || !lag || !prob || !hash || !out || timestep < 0) return DRAGG_E_ARG;
+    if (dims->n_groups > 1) return DRAGG_E_ARG;                       // grouped batches: dragg_mpc_step only
     if (dims->n_homes == 0) return DRAGG_OK;
     if (!lag->clock || !lag->skipped || !lag->narrow || (side && !lag->side_workspace) || !prob->params ||
         !prob->home_type || !prob->oat || !prob->ghi || !prob->tou || !prob->reward_price || !prob->draw_hourly ||
@@ -5316,6 +5382,7 @@ int dragg_mpc_step_side(const dragg_mpc_dims* dims, const dragg_mpc_problem* pro
 
 int dragg_mpc_lag_reset(const dragg_mpc_dims* dims, const dragg_mpc_lag* lag, int32_t timestep, void* stream) {
     if (!dims || dims->n_homes < 0 || !lag || timestep < 0 || timestep >= LAG_SIDE - 1) return DRAGG_E_ARG;
+    if (dims->n_groups > 1) return DRAGG_E_ARG;
     if (dims->n_homes == 0) return DRAGG_OK;
     if (!lag->clock) return DRAGG_E_ARG;
     hipLaunchKernelGGL(lag_reset_kernel, dim3((dims->n_homes + 255) / 256), dim3(256), 0, (hipStream_t)stream,
@@ -5338,6 +5405,7 @@ int dragg_mpc_solve_explicit(const dragg_mpc_dims* dims, const dragg_mpc_problem
                              void* stream) {
     int rc = check_dims(dims);
     if (rc) return rc;
+    if (dims->n_groups > 1) return DRAGG_E_ARG;                       // (explicit inputs carry no price list)
     if (dims->n_homes == 0) return (prob && in && hash && out) ? DRAGG_OK : DRAGG_E_ARG;
     if (!prob || !in || !hash || !out || !prob->params || !prob->home_type || !in->t || !in->T0 ||
         !in->Tw0 || !in->E0 || !in->counter || !in->winter || !in->draw || !in->oat || !in->ghi ||
@@ -5347,7 +5415,7 @@ int dragg_mpc_solve_explicit(const dragg_mpc_dims* dims, const dragg_mpc_problem
     if (direct_mode(dims) && !prob->workspace) return DRAGG_E_ARG;
     KArgs a{};
     a.d = *dims; a.p = *prob; a.ex = *in; a.vals = hash->vals; a.fc = hash->fc; a.out = *out;
-    return launch<true>(a, (hipStream_t)stream);
+    return launch<PM_EXPLICIT>(a, (hipStream_t)stream);
 }
 
 void dragg_mpc_reload_knobs(void) { g_knobs = read_knobs(); }
@@ -5395,11 +5463,45 @@ int dragg_mpc_aggregate(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, 
 int dragg_mpc_season_noise(const dragg_mpc_dims* dims, uint64_t seed, int32_t home_offset, int32_t home_stride,
                            int32_t timestep, double* noise_out, void* stream) {
     if (!dims || dims->n_homes < 0 || dims->horizon < 1) return DRAGG_E_ARG;
+    if (dims->n_groups < 0 || (dims->n_groups > 1 && dims->n_homes % dims->n_groups != 0)) return DRAGG_E_ARG;
     const int total = dims->n_homes * ((dims->horizon + 1) / 2);
     if (total == 0) return DRAGG_OK;
     if (!noise_out) return DRAGG_E_ARG;
     hipLaunchKernelGGL(noise_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                       dims->n_homes, dims->horizon, seed, home_offset, max(home_stride, 1), timestep, noise_out);
+                       dims->n_homes, dims->horizon, seed, home_offset, max(home_stride, 1), timestep, noise_out,
+                       dims->n_homes / max(dims->n_groups, 1));
+    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+}
+
+int dragg_mpc_replicate(const dragg_mpc_dims* dims, const dragg_mpc_hash* src_hash, dragg_mpc_hash* dst_hash,
+                        void* stream) {
+    if (!dims || dims->n_homes < 0 || dims->horizon < 1 || dims->n_groups < 0 || !src_hash || !dst_hash)
+        return DRAGG_E_ARG;
+    const int G = max(dims->n_groups, 1);
+    if (dims->n_homes % G != 0) return DRAGG_E_ARG;
+    if (dims->n_homes == 0) return DRAGG_OK;
+    if (!src_hash->vals || !src_hash->fc || !dst_hash->vals || !dst_hash->fc) return DRAGG_E_ARG;
+    const long long Nb = dims->n_homes / G;
+    auto seg = [&](const double* s, double* d, long long R, int rows) {
+        const bool wide = R % 2 == 0 && (reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d)) % 16 == 0;
+        return RepSeg{s, d, R, rows * R / (wide ? 2 : 1), rows, wide ? 1 : 0};
+    };
+    const RepSeg v = seg(src_hash->vals, dst_hash->vals, Nb, DRAGG_NVAL);
+    const RepSeg f = seg(src_hash->fc, dst_hash->fc, Nb * DRAGG_NFC * dims->horizon, 1);
+    const long long blocks = (v.units + f.units + REP_NT - 1) / REP_NT;
+    hipLaunchKernelGGL(replicate_kernel, dim3((unsigned)min(blocks, (long long)REP_BLOCKS_MAX)), dim3(REP_NT), 0,
+                       (hipStream_t)stream, v, f, G);
+    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+}
+
+int dragg_mpc_aggregate_groups(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, double* out, void* stream) {
+    // n_homes == 0: every group's sums are zero (vals may be NULL)
+    if (!dims || !hash || (!hash->vals && dims->n_homes > 0) || !out || dims->n_homes < 0 || dims->n_groups < 0)
+        return DRAGG_E_ARG;
+    const int G = max(dims->n_groups, 1);
+    if (dims->n_homes % G != 0) return DRAGG_E_ARG;
+    hipLaunchKernelGGL(aggregate_groups_kernel, dim3(G), dim3(AGG_NT), 0, (hipStream_t)stream, hash->vals,
+                       dims->n_homes, dims->n_homes / G, out);
     return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
 }
 

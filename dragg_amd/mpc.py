@@ -104,13 +104,20 @@ class MPCBatch:
         than one duty step -- ~0.3 homes per 10k-home step --, mixed-sign prices without a usable
         bound, RL fronts past 2,048 labels) by the exact step-function DP (slow) instead of the
         bucketed DP's schedule (DRAGG_FLAG_EXACT).  Statuses are exact either way.
+    groups : G > 1 makes a grouped batch (dims.n_groups, include/dragg_mi355x.h): G consecutive
+        replicas of `homes` (N = G * len(homes), self.Nb = len(homes)), replica g solved under row g
+        of the reward price ([G][n]) with its base homes' season noise -- G candidate prices against
+        one community in one launch.  Its state comes from a base batch (`replicate_from`), its sums
+        per group from `aggregate_groups`; `step` is its only solve (no lag mode, no explicit inputs).
     """
 
     def __init__(self, homes, oat=None, ghi=None, tou=None, start_index=0, reward_price=(0.0,),
                  int_mode="round", seed=0, max_iter=4000, check_every=10, device="cuda", home_offset=0,
-                 home_stride=1, template_home=None, exact=False):
+                 home_stride=1, template_home=None, exact=False, groups=1):
         if int_mode not in L.INT_MODES:
             raise ValueError(f"int_mode must be one of {sorted(L.INT_MODES)}, not {int_mode!r}")
+        if int(groups) < 1:
+            raise ValueError(f"groups must be >= 1, not {groups!r}")
         self.lib = L.load()
         if not torch.cuda.is_available():
             raise L.DraggError("no GPU visible: the batched MPC has no CPU fallback")
@@ -120,7 +127,10 @@ class MPCBatch:
         self.homes = homes
         self.names = [h["name"] for h in homes]
         P, types, draws, dm = pack_homes(homes, template_home)
-        self.N, self.H, self.S, self.dt = len(homes), dm["H"], dm["S"], dm["dt"]
+        self.groups, self.Nb = int(groups), len(homes)
+        if self.groups > 1:                 # replica g of base home i is home g * Nb + i
+            P, types, draws = np.tile(P, (1, self.groups)), np.tile(types, self.groups), np.tile(draws, (1, self.groups))
+        self.N, self.H, self.S, self.dt = self.groups * len(homes), dm["H"], dm["S"], dm["dt"]
         dev = self.device
         self.params = torch.tensor(P, dtype=torch.float64, device=dev).contiguous()
         self.types = torch.tensor(types, dtype=torch.int32, device=dev)
@@ -130,7 +140,7 @@ class MPCBatch:
                            n_draw_hours=dm["n_draw_hours"], n_env=0, n_rp=1,
                            int_mode=L.INT_MODES[int_mode],
                            max_iter=max_iter, check_every=check_every, discount=dm["discount"],
-                           flags=L.FLAG_EXACT if exact else 0)
+                           flags=L.FLAG_EXACT if exact else 0, n_groups=self.groups if self.groups > 1 else 0)
         self.seed = int(seed)
         self.home_offset = int(home_offset)
         self.home_stride = int(home_stride)
@@ -173,8 +183,20 @@ class MPCBatch:
 
     def set_reward_price(self, rp):
         """The redis 'reward_price' list (mpc_calc.py:630-637): host values, or a device tensor
-        (e.g. an RL action broadcast over RCCL), taken without a host round trip."""
-        if torch.is_tensor(rp):
+        (e.g. an RL action broadcast over RCCL), taken without a host round trip.  A grouped batch
+        takes [G][n], one list per group (every row n entries), or one list for every group."""
+        G = getattr(self, "groups", 1)
+        if G > 1:
+            if not torch.is_tensor(rp):
+                rp = torch.as_tensor(np.asarray(rp, dtype=float), dtype=torch.float64)
+            rp = rp.detach().to(device=self.device, dtype=torch.float64)
+            if rp.dim() < 2:
+                rp = rp.reshape(1, -1).expand(G, -1)
+            if rp.dim() != 2 or rp.shape[0] != G:
+                raise ValueError(f"a batch of {G} groups takes reward prices [{G}][n], not {list(rp.shape)}")
+            n = rp.shape[1]
+            rp = rp.reshape(-1).contiguous()
+        elif torch.is_tensor(rp):
             rp = rp.detach().to(device=self.device, dtype=torch.float64).reshape(-1).contiguous()
             n = rp.numel()
         else:
@@ -251,6 +273,8 @@ class MPCBatch:
         step t), the side stream and the events that order the two passes."""
         if self.dims.int_mode not in (L.INT_ROUND, L.INT_FAIL):
             raise ValueError("lag mode needs int_mode 'round' (or 'fail')")
+        if self.groups > 1:
+            raise ValueError("a grouped batch has no lag mode (dragg_mpc_step only)")
         dev = self.device
         with torch.cuda.device(dev):
             self.lag = {
@@ -337,7 +361,10 @@ class MPCBatch:
 
     def _step(self, t, noise, hist, stream):
         if noise is not None:
-            noise = noise.to(device=self.device, dtype=torch.float64).contiguous()
+            noise = noise.to(device=self.device, dtype=torch.float64)
+            if self.groups > 1 and tuple(noise.shape) == (self.H, self.Nb):
+                noise = noise.repeat(1, self.groups)        # the base homes' draws, for every replica
+            noise = noise.contiguous()
             assert tuple(noise.shape) == (self.H, self.N)
         prob, hsh, out = self._problem(), self._hash(), self._out(hist)
         L.check(self.lib.dragg_mpc_step(ctypes.byref(self.dims), ctypes.byref(prob), ctypes.byref(hsh),
@@ -385,6 +412,30 @@ class MPCBatch:
         L.check(self.lib.dragg_mpc_aggregate(ctypes.byref(self.dims), ctypes.byref(hsh), L.ptr(self.agg),
                                              L.stream_ptr(stream, self.device)))
         return self.agg
+
+    # ------------------------------------------------------------------ grouped batches
+    def replicate_from(self, base, stream=None):
+        """Copy `base`'s hash arrays (vals, fc: the state a step reads) into every replica of this
+        grouped batch, bit for bit, in one kernel (dragg_mpc_replicate).  `base` is only read."""
+        if base.N * self.groups != self.N or base.H != self.H:
+            raise ValueError(f"replicate_from: {self.groups} replicas of {self.Nb} homes (H = {self.H}) cannot "
+                             f"take a batch of {base.N} homes (H = {base.H})")
+        with torch.cuda.device(self.device):
+            base.drain(stream)
+            src, dst = base._hash(), self._hash()
+            L.check(self.lib.dragg_mpc_replicate(ctypes.byref(self.dims), ctypes.byref(src), ctypes.byref(dst),
+                                                 L.stream_ptr(stream, self.device)))
+
+    def aggregate_groups(self, stream=None):
+        """collect_data's sums of every group -> device tensor [G][3]; row g is bit-identical to
+        aggregate() of a batch holding replica g's homes (dragg_mpc_aggregate_groups)."""
+        with torch.cuda.device(self.device):
+            if getattr(self, "agg_groups", None) is None:
+                self.agg_groups = torch.zeros((self.groups, 3), dtype=torch.float64, device=self.device)
+            hsh = self._hash()
+            L.check(self.lib.dragg_mpc_aggregate_groups(ctypes.byref(self.dims), ctypes.byref(hsh),
+                                                        L.ptr(self.agg_groups), L.stream_ptr(stream, self.device)))
+            return self.agg_groups
 
     def season_noise(self, t, stream=None):
         with torch.cuda.device(self.device):

@@ -250,14 +250,17 @@ class Aggregator:
         self.agg_setpoint = self.gen_setpoint()
         return agg
 
-    def _set_price(self, reward_price):
+    def _price_list(self, reward_price):
         rp = np.asarray(reward_price, dtype=float).reshape(-1)
         if len(rp) == 1:
             rp = np.full(len(self.reward_price), rp[0])
         if len(rp) != len(self.reward_price):
             raise ValueError(f"reward price has {len(rp)} entries, the action horizon holds "
                              f"{len(self.reward_price)} (agg.rl.action_horizon * dt)")
-        self.reward_price = rp
+        return rp
+
+    def _set_price(self, reward_price):
+        self.reward_price = self._price_list(reward_price)
 
     def rl_step(self, reward_price):
         """One RL-aggregator timestep under `reward_price` (a scalar, or action_horizon*dt
@@ -285,6 +288,21 @@ class Aggregator:
             self.dev.set_reward_price(prev)
         return out.cpu().numpy()
 
+    def rl_sweep(self, prices, steps=None):
+        """The community's response to each of G candidate prices (scalars, or lists of
+        action_horizon*dt values) over `rl.forecast_horizon` timesteps, all candidates solved together
+        on device (`DeviceAggregator.sweep`): what G `rl_forecast` calls return, bit for bit, without
+        their snapshots and restores.  Nothing is committed and `self.reward_price` stays.
+        -> [G][steps][agg_load, forecast_load, agg_cost] on the host; the candidates' solve-path counts
+        are in `self.dev.sweep_counts`."""
+        steps = int(self.config["agg"]["rl"]["forecast_horizon"]) if steps is None else int(steps)
+        steps = min(steps, self.num_timesteps - self.dev.timestep)
+        rows = [self._price_list(p) for p in prices]
+        if not rows:
+            raise ValueError("rl_sweep needs at least one candidate price")
+        out = self.dev.sweep(np.stack(rows), steps, noise_fn=self._noise if getattr(self, "noise_fn", None) else None)
+        return out.cpu().numpy()
+
     # aggregator.py:898-911
     def test_response(self):
         c = self.config["agg"]["simplified"]["response_rate"]
@@ -298,7 +316,7 @@ class Aggregator:
         """The `run_rl_agg` case (README.md:55): MPC homes under an RL-designed reward price.
         `policy(aggregator) -> reward price` is called once per timestep (e.g. an
         `dragg_amd.rl.SetpointAgent.act`, or the reference's agent via `rl.policy_from_agent`);
-        it may call `rl_forecast` to try candidate prices.
+        it may call `rl_forecast` to try a candidate price, or `rl_sweep` to try several at once.
         Writes `<run dir>/rl_agg/results.json` with the Summary's RP and p_grid_setpoint."""
         self.case = "rl_agg"
         self.get_homes()

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define DRAGG_MPC_ABI_VERSION 9
+#define DRAGG_MPC_ABI_VERSION 10
 
 /* home types (aggregator.py:425, 468, 520, 555); bit 0 = pv, bit 1 = battery */
 enum dragg_home_type {
@@ -133,7 +133,19 @@ typedef struct dragg_mpc_dims {
     int32_t check_every;   /* polish / residual check interval (<=0: default 10)       */
     double discount;       /* discount_factor                        (mpc_calc.py:152) */
     int32_t flags;         /* dragg_flag bits (0 = default)                             */
-    int32_t reserved;
+    int32_t n_groups;      /* G (since v10; 0 or 1 = one community, as before).  G > 1: a
+                              grouped batch -- the n_homes homes are G consecutive replicas
+                              of Nb = n_homes / G base homes (n_homes % G == 0): home r is
+                              replica (group) r / Nb of base home r % Nb.  Group g is solved
+                              under row g of problem.reward_price ([G][n_rp]) and draws the
+                              keyed season noise of its BASE home (global home home_offset +
+                              base * home_stride), so G candidate prices are solved against
+                              one community in one dragg_mpc_step.  Every per-home array
+                              (params, home_type, draw_hourly, vals, fc, the outputs, an
+                              explicit noise array) is n_homes wide as always: the caller
+                              tiles the base community's G times (state: dragg_mpc_replicate).
+                              dragg_mpc_step only: dragg_mpc_solve_explicit and the lag-mode
+                              entry points return DRAGG_E_ARG for G > 1                    */
 } dragg_mpc_dims;
 
 /* dims.flags */
@@ -154,9 +166,11 @@ typedef struct dragg_mpc_problem {
     const double* oat;          /* [n_env] redis 'OAT' list                             */
     const double* ghi;          /* [n_env] redis 'GHI' list                             */
     const double* tou;          /* [n_env] redis 'tou' list                             */
-    const double* reward_price; /* [n_rp]  redis 'reward_price' list                    */
+    const double* reward_price; /* [n_rp]  redis 'reward_price' list; a grouped batch    */
+                                /* (dims.n_groups = G > 1): [G][n_rp], row g = group g's */
     int32_t start_index;        /* start_hour_index (aggregator.py:630-638)             */
-    int32_t home_offset;        /* global index of home 0 of this shard (noise key)     */
+    int32_t home_offset;        /* global index of home 0 of this shard (noise key; a    */
+                                /* grouped batch: of base home 0)                        */
     uint64_t seed;              /* keyed season-noise stream when noise == NULL         */
     void* workspace;            /* device scratch, dragg_mpc_workspace_bytes(dims) bytes */
                                 /* (int_mode round: DP back-pointers); may be NULL when  */
@@ -298,6 +312,22 @@ int dragg_mpc_kernel_info_get(const dragg_mpc_dims* dims, dragg_mpc_kernel_info*
 int dragg_mpc_aggregate(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, double* out3,
                         void* stream);
 
+/* Fan a base batch's state out to a grouped batch (since v10): `dims` describes the grouped batch
+   (n_homes = G * Nb, n_groups = G; G <= 1: a plain copy), src_hash holds the base batch's vals
+   [DRAGG_NVAL][Nb] and fc [Nb][DRAGG_NFC][H], dst_hash the grouped batch's vals [DRAGG_NVAL][G * Nb] and
+   fc [G * Nb][DRAGG_NFC][H].  Every replica receives its base home's fields bit for bit (NaN payloads
+   included: NaN = field absent).  One kernel: each source element is read once and stored G times.
+   src_hash is only read. */
+int dragg_mpc_replicate(const dragg_mpc_dims* dims, const dragg_mpc_hash* src_hash,
+                        dragg_mpc_hash* dst_hash, void* stream);
+
+/* collect_data's sums of every group of a grouped batch (since v10): out[G][3], row g exactly as
+   dragg_mpc_aggregate on a batch holding group g's Nb homes (the same lanes and reduction order:
+   bit-identical); a NaN makes only its own group's sum NaN.  G <= 1: one row, dragg_mpc_aggregate's.
+   n_homes == 0: zeros. */
+int dragg_mpc_aggregate_groups(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, double* out,
+                               void* stream);
+
 /* Lag mode (since v8): run_rbo_mpc's timestep loop (aggregator.py:757-778) has no feedback between
    homes, so a home whose chain needs the slow exact step-function DP need not hold up the others.
    A step is split into two passes the caller puts on two streams:
@@ -339,7 +369,8 @@ int dragg_mpc_aggregate_rows(const dragg_mpc_dims* dims, const double* rows, int
 
 /* The keyed season-noise stream used when noise == NULL: writes [H][N] normals for
    timestep t (exposed so the host and tests can reproduce the draw); home i of the shard
-   draws the stream of global home home_offset + i*home_stride (home_stride 0 = 1). */
+   draws the stream of global home home_offset + i*home_stride (home_stride 0 = 1); in a grouped
+   batch (dims.n_groups > 1) home i draws its base home's, i % Nb in place of i. */
 int dragg_mpc_season_noise(const dragg_mpc_dims* dims, uint64_t seed, int32_t home_offset,
                            int32_t home_stride, int32_t timestep, double* noise_out, void* stream);
 

@@ -1,0 +1,333 @@
+"""Price sweep on the GPU (ABI v10): a grouped batch (dims.n_groups = G) solves G replicas of a
+community under G reward-price lists in one dragg_mpc_step.
+
+* `DeviceAggregator.sweep` equals `forecast` under each candidate, bit for bit (the same code on the
+  same inputs), in int_mode round (TOU, cell / mid / big paths side by side) and relax;
+* it reads the live state and never writes it; every replica home equals the base home stepped under
+  its price;
+* dragg_mpc_replicate copies bit for bit at unaligned replica offsets (NaN payloads included),
+  dragg_mpc_aggregate_groups sums each group exactly as dragg_mpc_aggregate sums its homes, and a
+  replica draws its base home's season noise;
+* the argument checks of the grouped layout, and the per-candidate solve-path counts."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+STEPS = 3
+
+
+def _prices():
+    rp = -0.03 * np.cos(np.arange(24))
+    return np.stack([np.zeros(24), rp, rp + 0.2])     # flat (the TOU path), RL-priced, RL-priced and shifted
+
+
+@pytest.fixture(scope="module")
+def community():
+    from dragg_amd.community import synthetic_homes, synthetic_weather
+    homes = synthetic_homes(64, seed=5, days=2, dt=4, horizon_hours=6)
+    assert {h["type"] for h in homes} == {"base", "pv_only", "battery_only", "pv_battery"}
+    return homes, synthetic_weather(2, 4, 24, seed=5, month=7)
+
+
+def _agg(community, n=64, steps=2, **kw):
+    """The community after `steps` committed steps under a zero reward price."""
+    from dragg_amd.aggregator import DeviceAggregator
+    homes, (oat, ghi, tou) = community
+    agg = DeviceAggregator(homes[:n], oat, ghi, tou, 0, 8, reward_price=[0.0] * 24, seed=5, **kw)
+    for _ in range(steps):
+        agg.run_iteration()
+        agg.collect_data()
+    return agg
+
+
+def _bits(x):
+    return x.contiguous().view(torch.int64)
+
+
+def _state(agg):
+    agg.drain()
+    b = agg.batch
+    return agg.timestep, _bits(b.vals).clone(), _bits(b.fc_store).clone(), b.rp.clone(), b.status.clone()
+
+
+def _state_equal(a, b):
+    return a[0] == b[0] and all(torch.equal(x, y) for x, y in zip(a[1:], b[1:]))
+
+
+@pytest.fixture(scope="module")
+def forecasts(gpu, community):
+    """forecast(STEPS) under each candidate, one at a time: what a sweep must reproduce."""
+    agg = _agg(community)
+    out = []
+    for p in _prices():
+        agg.set_reward_price(p)
+        out.append(agg.forecast(STEPS).clone())
+    return torch.stack(out)
+
+
+def test_sweep_equals_forecast(gpu, community, forecasts):
+    agg = _agg(community)
+    sw = agg.sweep(_prices(), STEPS)
+    assert tuple(sw.shape) == (3, STEPS, 3) and not torch.isnan(sw).any()
+    for g in range(3):
+        assert torch.equal(sw[g], forecasts[g]), g
+    assert not torch.equal(sw[0], sw[1]) and not torch.equal(sw[1], sw[2])
+    c = agg.sweep_counts
+    assert all(len(c[k]) == 3 for k in ("approx_solves", "step_dp_solves", "later_launch_solves"))
+    # again, from the cached replica batch: the same
+    assert torch.equal(agg.sweep(_prices(), STEPS), sw)
+
+
+def test_sweep_leaves_live_state_untouched(gpu, community):
+    rp = _prices()[1]
+    agg, ref = _agg(community), _agg(community)
+    agg.set_reward_price(rp)
+    ref.set_reward_price(rp)
+    before = _state(agg)
+    hist_before = (agg.hist.clone().nan_to_num(7.7), agg.agg_hist.clone(), agg.status_hist.clone(),
+                   agg.path_hist.clone())
+    agg.sweep(_prices(), STEPS)
+    assert _state_equal(before, _state(agg))
+    assert torch.equal(agg.hist.nan_to_num(7.7), hist_before[0]) and torch.equal(agg.agg_hist, hist_before[1])
+    assert torch.equal(agg.status_hist, hist_before[2]) and torch.equal(agg.path_hist, hist_before[3])
+    for _ in range(STEPS):                              # the steps committed afterwards: a run that never swept
+        agg.run_iteration()
+        ref.run_iteration()
+        assert torch.equal(agg.collect_data(), ref.collect_data())
+    assert _state_equal(_state(agg), _state(ref))
+
+
+def test_replica_homes_equal_base_homes(gpu, community):
+    from dragg_amd import _lib as L
+    agg = _agg(community)
+    agg.sweep(_prices(), 1)
+    rb = agg._sweep_batches[3]
+    Nb = agg.batch.N
+    assert rb.N == 3 * Nb and rb.dims.n_groups == 3
+    counts = agg.sweep_counts
+    for g, p in enumerate(_prices()):
+        base = _agg(community)
+        base.set_reward_price(p)
+        base.batch.step(base.timestep)
+        b, sl = base.batch, slice(g * Nb, (g + 1) * Nb)
+        assert torch.equal(rb.status[sl], b.status), g
+        assert torch.equal(_bits(rb.obj[sl]), _bits(b.obj)), g
+        assert torch.equal(rb.int_path[sl], b.int_path), g
+        assert torch.equal(_bits(rb.vals[:, sl]), _bits(b.vals)), g
+        assert torch.equal(_bits(rb.fc_store[sl]), _bits(b.fc_store)), g
+        # the candidate's counts are its own homes' (the masks of approx_counts)
+        path = b.int_path
+        assert counts["approx_solves"][g] == int(((path & L.PATH_APPROX_MASK) != 0).sum())
+        assert counts["step_dp_solves"][g] == int(((path & L.PATH_STEPS) != 0).sum())
+        assert counts["later_launch_solves"][g] == int(((path & L.PATH_SECOND) != 0).sum())
+
+
+# ------------------------------------------------------------------ dragg_mpc_replicate
+def _replicate_raw(L, lib, src_vals, src_fc, G, H):
+    """dragg_mpc_replicate on raw int64 bit patterns ([NVAL][Nb], [Nb][NFC][H]) -> the replicas' arrays."""
+    Nb = src_vals.shape[1]
+    dims = L.Dims(n_homes=G * Nb, horizon=H, sub_steps=6, dt=4, n_groups=G)
+    dst_vals = torch.full((L.NVAL, G * Nb), -1, dtype=torch.int64, device=src_vals.device)
+    dst_fc = torch.full((G * Nb, L.NFC, H), -1, dtype=torch.int64, device=src_vals.device)
+    src, dst = L.Hash(vals=L.ptr(src_vals), fc=L.ptr(src_fc)), L.Hash(vals=L.ptr(dst_vals), fc=L.ptr(dst_fc))
+    L.check(lib.dragg_mpc_replicate(ctypes.byref(dims), ctypes.byref(src), ctypes.byref(dst), L.stream_ptr()))
+    return dst_vals, dst_fc
+
+
+# (Nb, G, H): unaligned replica offsets with 8-byte vals and 16-byte fc units; every unit 8 bytes (Nb * NFC * H
+# odd); one home; a plain copy (G = 1); more units than one pass of the kernel's grid
+@pytest.mark.parametrize("Nb,G,H", [(7, 3, 24), (7, 3, 3), (1, 3, 24), (64, 1, 24), (6001, 2, 24)])
+def test_replicate_raw_bits(gpu, Nb, G, H):
+    from dragg_amd import _lib as L
+    lib = L.load()
+    gen = torch.Generator(device="cpu").manual_seed(Nb * 131 + G)
+    # any bit pattern, NaNs with payloads among them
+    vals = torch.randint(-2 ** 62, 2 ** 62, (L.NVAL, Nb), generator=gen, dtype=torch.int64)
+    fc = torch.randint(-2 ** 62, 2 ** 62, (Nb, L.NFC, H), generator=gen, dtype=torch.int64)
+    vals[3, 0] = 0x7FF8000000000ABC
+    fc[0, 2, H - 1] = 0x7FF0000000000001 - 2 ** 63      # a signalling NaN, sign bit set
+    vals, fc = vals.to(gpu), fc.to(gpu)
+    dv, df = _replicate_raw(L, lib, vals, fc, G, H)
+    for g in range(G):
+        assert torch.equal(dv[:, g * Nb:(g + 1) * Nb], vals), g
+        assert torch.equal(df[g * Nb:(g + 1) * Nb], fc), g
+
+
+@pytest.mark.parametrize("Nb,G", [(7, 3), (1, 3), (64, 1)])
+def test_replicate_from_batch_states(gpu, community, Nb, G):
+    from dragg_amd.mpc import MPCBatch
+    homes, (oat, ghi, tou) = community
+    base = MPCBatch(homes[:Nb], oat, ghi, tou, 0, [0.0], seed=5)
+    rb = MPCBatch(homes[:Nb], oat, ghi, tou, 0, [0.0], seed=5, groups=G)
+    assert (rb.N, rb.Nb, rb.groups) == (G * Nb, Nb, G) and rb.dims.n_groups == (G if G > 1 else 0)
+    for solved in (False, True):
+        if solved:
+            base.step(0)
+            assert not torch.isnan(base.vals).all()
+        else:
+            assert torch.isnan(base.vals).all() and torch.isnan(base.fc_store).all()   # t = 0: every field absent
+        rb.vals.fill_(1.0)
+        rb.fc_store.fill_(1.0)
+        rb.replicate_from(base)
+        for g in range(G):
+            assert torch.equal(_bits(rb.vals[:, g * Nb:(g + 1) * Nb]), _bits(base.vals)), (solved, g)
+            assert torch.equal(_bits(rb.fc_store[g * Nb:(g + 1) * Nb]), _bits(base.fc_store)), (solved, g)
+    with pytest.raises(ValueError):
+        rb.replicate_from(MPCBatch(homes[:2] if Nb == 1 else homes[:Nb - 1], oat, ghi, tou, 0, [0.0], seed=5))
+
+
+# ------------------------------------------------------------------ dragg_mpc_aggregate_groups
+@pytest.mark.parametrize("Nb", [7, 1500])              # 1,500: more than one pass of the 1,024-thread block
+def test_aggregate_groups_equals_aggregate(gpu, Nb):
+    from dragg_amd import _lib as L
+    lib, G = L.load(), 3
+    gen = torch.Generator(device="cpu").manual_seed(Nb)
+    vals = ((torch.rand((L.NVAL, G * Nb), generator=gen, dtype=torch.float64) - 0.3) * 10.0).to(gpu)
+
+    def groups(v):
+        dims = L.Dims(n_homes=G * Nb, horizon=24, sub_steps=6, dt=4, n_groups=G)
+        out = torch.full((G, 3), 99.0, dtype=torch.float64, device=gpu)
+        h = L.Hash(vals=L.ptr(v), fc=None)
+        L.check(lib.dragg_mpc_aggregate_groups(ctypes.byref(dims), ctypes.byref(h), L.ptr(out), L.stream_ptr()))
+        return out
+
+    def one(v, g):
+        part = v[:, g * Nb:(g + 1) * Nb].contiguous()
+        dims = L.Dims(n_homes=Nb, horizon=24, sub_steps=6, dt=4)
+        out = torch.full((3,), 99.0, dtype=torch.float64, device=gpu)
+        h = L.Hash(vals=L.ptr(part), fc=None)
+        L.check(lib.dragg_mpc_aggregate(ctypes.byref(dims), ctypes.byref(h), L.ptr(out), L.stream_ptr()))
+        torch.cuda.synchronize()
+        return out
+
+    got = groups(vals)
+    for g in range(G):
+        assert torch.equal(got[g], one(vals, g)), g
+    np.testing.assert_allclose(got[:, 0].cpu().numpy(),
+                               vals[L.K["p_grid_opt"]].view(G, Nb).sum(1).cpu().numpy(), rtol=1e-12)
+    vals[L.K["cost_opt"], Nb + min(3, Nb - 1)] = float("nan")          # an absent field in group 1
+    bad = groups(vals)
+    assert torch.isnan(bad[1, 2]) and torch.isnan(bad).sum() == 1
+    keep = ~torch.isnan(bad)
+    assert torch.equal(bad[keep], got[keep])
+    assert torch.equal(_bits(bad[1]), _bits(one(vals, 1)))
+
+
+# ------------------------------------------------------------------ season noise
+@pytest.mark.parametrize("off,stride", [(0, 1), (3, 2)])
+def test_grouped_season_noise_is_the_base_homes(gpu, off, stride):
+    from dragg_amd import _lib as L
+    lib, Nb, G, H = L.load(), 5, 3, 24
+
+    def noise(n, groups):
+        dims = L.Dims(n_homes=n, horizon=H, sub_steps=6, dt=4, n_groups=groups)
+        out = torch.zeros((H, n), dtype=torch.float64, device=gpu)
+        L.check(lib.dragg_mpc_season_noise(ctypes.byref(dims), 11, off, stride, 4, L.ptr(out), L.stream_ptr()))
+        return out
+
+    base, grouped = noise(Nb, 0), noise(G * Nb, G)
+    assert base.std() > 0.5
+    for g in range(G):
+        assert torch.equal(grouped[:, g * Nb:(g + 1) * Nb], base), g
+    assert not torch.equal(noise(G * Nb, 0)[:, Nb:2 * Nb], base)       # (ungrouped: 15 homes of their own)
+
+
+# ------------------------------------------------------------------ other modes
+def test_sweep_equals_forecast_relax(gpu, community):
+    agg = _agg(community, n=16, steps=1, int_mode="relax")
+    P = _prices()[1:]
+    per = []
+    for p in P:
+        agg.set_reward_price(p)
+        per.append(agg.forecast(1).clone())
+    sw = agg.sweep(P, 1)
+    assert tuple(sw.shape) == (2, 1, 3) and torch.equal(sw, torch.stack(per))
+    assert not torch.equal(sw[0], sw[1])
+
+
+# ------------------------------------------------------------------ argument checks
+def test_grouped_argument_checks(gpu, community):
+    from dragg_amd import _lib as L
+    from dragg_amd.mpc import MPCBatch
+    homes, (oat, ghi, tou) = community
+    lib = L.load()
+    E_ARG = -1
+    rb = MPCBatch(homes[:4], oat, ghi, tou, 0, [0.0], seed=5, groups=2)
+
+    def dims_of(b, **kw):
+        d = L.Dims.from_buffer_copy(b.dims)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+    # n_homes % n_groups != 0, n_groups < 0
+    for bad in (dims_of(rb, n_groups=3), dims_of(rb, n_groups=-1)):
+        assert lib.dragg_mpc_workspace_bytes(ctypes.byref(bad)) == E_ARG
+        prob, hsh, out = rb._problem(), rb._hash(), rb._out()
+        assert lib.dragg_mpc_step(ctypes.byref(bad), ctypes.byref(prob), ctypes.byref(hsh), ctypes.byref(out), 0,
+                                  None, L.stream_ptr()) == E_ARG
+        assert lib.dragg_mpc_replicate(ctypes.byref(bad), ctypes.byref(hsh), ctypes.byref(hsh), L.stream_ptr()) == E_ARG
+        assert lib.dragg_mpc_aggregate_groups(ctypes.byref(bad), ctypes.byref(hsh), L.ptr(rb.agg),
+                                              L.stream_ptr()) == E_ARG
+        assert lib.dragg_mpc_season_noise(ctypes.byref(bad), 1, 0, 1, 0, L.ptr(rb.obj), L.stream_ptr()) == E_ARG
+    assert lib.dragg_mpc_workspace_bytes(ctypes.byref(dims_of(rb))) > 0
+    # the explicit entry point: fine for the base batch, DRAGG_E_ARG for the grouped one
+    for b, ok in ((MPCBatch(homes[:4], oat, ghi, tou, 0, [0.0], seed=5), True), (rb, False)):
+        n, H = b.N, b.H
+        P = b.params.cpu().numpy()
+        ex = dict(t=np.zeros(n, np.int32), T0=P[L.P["TINIT"]], Tw0=P[L.P["TWINIT"]], E0=P[L.P["EINIT"]],
+                  counter=np.zeros(n, np.int32), winter=np.ones(n, np.int32), draw=np.zeros((H + 1, n)),
+                  oat=np.full((H + 1, n), 5.0), ghi=np.zeros((H + 1, n)), price=np.full((H, n), 0.1))
+        if ok:
+            b.solve_explicit(**ex)
+        else:
+            with pytest.raises(L.DraggError, match="invalid argument"):
+                b.solve_explicit(**ex)
+    # the lag-mode entry points
+    with pytest.raises(ValueError):
+        rb.enable_lag()
+    b = MPCBatch(homes[:4], oat, ghi, tou, 0, [0.0], seed=5)
+    b.enable_lag(ring=2)
+    b.rp = torch.zeros(2, dtype=torch.float64, device=gpu)            # (a row per group)
+    lg = b.lag
+    lag = L.Lag(clock=L.ptr(lg["clock"]), skipped=L.ptr(lg["lists"][0, 0]), narrow=L.ptr(lg["lists"][0, 1]),
+                side_workspace=L.ptr(lg["side_ws"]))
+    grouped = dims_of(b, n_groups=2)
+    prob, hsh, out = b._problem(), b._hash(), b._out()
+    sp = L.stream_ptr()
+    assert lib.dragg_mpc_lag_reset(ctypes.byref(b.dims), ctypes.byref(lag), 0, sp) == 0
+    assert lib.dragg_mpc_lag_reset(ctypes.byref(grouped), ctypes.byref(lag), 0, sp) == E_ARG
+    for f in (lib.dragg_mpc_step_main, lib.dragg_mpc_step_side):
+        assert f(ctypes.byref(grouped), ctypes.byref(prob), ctypes.byref(hsh), ctypes.byref(out), 0,
+                 ctypes.byref(lag), sp) == E_ARG
+    torch.cuda.synchronize()
+
+
+def test_sweep_of_an_empty_shard_is_zeros(gpu, community):
+    agg = _agg((community[0][:2], community[1]), n=2, steps=0, rank=2, world=3)   # more ranks than homes
+    assert agg.batch.N == 0
+    agg.world = 1                        # (no process group here: the collectives are not what is tested)
+    sw = agg.sweep(_prices(), STEPS)
+    assert tuple(sw.shape) == (3, STEPS, 3) and torch.equal(sw, torch.zeros_like(sw))
+    assert agg.sweep_counts["approx_solves"] == [0, 0, 0]
+
+
+# ------------------------------------------------------------------ sweep_counts
+def test_sweep_counts_per_candidate(gpu, community):
+    from dragg_amd import _lib as L
+    agg = _agg(community, n=16)
+    os.environ["DRAGG_FORCE_STEP_DP"] = "1"
+    L.reload_knobs()                     # (the library reads its knobs at load, never per step)
+    try:
+        agg.sweep(_prices(), 1)
+        c = agg.sweep_counts
+    finally:
+        os.environ.pop("DRAGG_FORCE_STEP_DP", None)
+        L.reload_knobs()
+    assert set(c) == {"approx_solves", "step_dp_solves", "later_launch_solves"}
+    assert all(len(v) == 3 for v in c.values())
+    assert all(n > 0 for n in c["step_dp_solves"]) and all(n <= 16 for n in c["step_dp_solves"])
