@@ -996,15 +996,23 @@ DEV bool dp_chain(const Home& h, const Lds& L, const DpChain& c, int lane) {
         glo = fmin(glo, L.lo[k * 8 + c.sx]);
         ghi = fmax(ghi, L.hi[k * 8 + c.sx]);
     }
-    const int cap = min(512, 12 * H);
+    // The four label arrays lie in zb..ybp (48H doubles >= 4 nb): at most 12H bins.  At S != 6 (every
+    // chain of round_lp comes here then, and a duty unit is small against the box at S > 6) the
+    // next-stage arrays may lie behind the back-pointers in Lf / Df (128H doubles) instead, which
+    // leaves zb..ybp to 24H bins but bounds them by 2 H nb + 16 nb <= 1024 H bytes: more bins than
+    // 12H up to H = 34 (twice as many up to H = 13), fewer beyond, so that layout is taken only
+    // where its cap is the larger one
+    const int cap12 = min(512, 12 * H), capw = min(512, min(24 * H, (512 * H) / (H + 8)));
+    const bool wide = S != 6 && capw > cap12;
+    const int cap = wide ? capw : cap12;
     double w = fabs(c.g) / NBU;
     int nb = (int)floor((ghi - glo) / w) + 1;
     if (nb > cap) { w = (ghi - glo) / (cap - 1); nb = cap; }
+    uint16_t* par = reinterpret_cast<uint16_t*>(L.Lf);   // [H][nb] (source bin << 4 | duty)
     double* cc = L.zb;                      // cost of the label in each bin
     double* cx = L.zb + nb;                 // its exact state
-    double* nc = L.zb + 2 * nb;
-    double* nx = L.zb + 3 * nb;             // zb..ybp are contiguous: 48H doubles >= 4 nb
-    uint16_t* par = reinterpret_cast<uint16_t*>(L.Lf);   // [H][nb] (source bin << 4 | duty)
+    double* nc = wide ? L.Lf + (H * nb + 3) / 4 : L.zb + 2 * nb;
+    double* nx = nc + nb;
     const double BIG = INFINITY;
     for (int k = 0; k < H; ++k) {
         const double Ak = c.A[k], Ck = c.C[k], ck = L.q[k * 8 + c.sv];

@@ -18,7 +18,12 @@ def load(name):
 def config_text(params):
     """The scenario's config.toml (tests/golden/config_template.toml, as make_golden.py wrote it)."""
     with open(os.path.join(GOLDEN, "config_template.toml")) as f:
-        return f.read().format(**params)
+        text = f.read().format(**params)
+    if "sub_steps" in params:               # the template's line says 6; a scenario may record another
+        line = "sub_subhourly_steps = 6\n"
+        assert text.count(line) == 1
+        text = text.replace(line, f"sub_subhourly_steps = {int(params['sub_steps'])}\n")
+    return text
 
 
 def scenarios():

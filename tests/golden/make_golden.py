@@ -63,13 +63,40 @@ SCENARIOS = {
     "negprice_dt2": dict(n=4, batt=1, pv=1, pvb=1, start="2015-01-01 00", end="2015-01-01 12",
                          dt=2, horizon=6, action_horizon=6, seed=13, record_t=range(0, 24),
                          rp=[round(0.11 * np.sin(0.5 * k) - 0.04, 4) for k in range(12)]),
+    # sub_subhourly_steps other than 6 ("sub_steps": the number of integer duty levels of a stage is
+    # S + 1; every scenario above runs the template's 6)
+    # (2 h horizon, 36 steps: at 15-minute steps an hourly draw is spread over four stages, and the
+    # first draw large enough to leave no schedule -- 255 L of a 256 L tank in the seventh hour --
+    # enters the forecast window at step 32; 7 of the 288 solves are infeasible)
+    "s4_dt4": dict(n=8, batt=2, pv=2, pvb=2, start="2015-01-01 00", end="2015-01-01 09",
+                   dt=4, horizon=2, action_horizon=2, seed=6, record_t=range(0, 36), sub_steps=4),
+    # binary duties
+    # (8 steps: from the fourth hour on most homes have no binary schedule left, and a fixture
+    # should have an optimum in at least half of its records)
+    "s1_dt1": dict(n=8, batt=2, pv=2, pvb=2, start="2015-04-02 00", end="2015-04-02 08",
+                   dt=1, horizon=6, action_horizon=6, seed=8, record_t=range(0, 8), sub_steps=1),
+    # mixed-sign reward prices; 18 steps, so that the large draws of the seventh hour enter the
+    # forecast window and two solves are infeasible
+    "s12_dt2": dict(n=6, batt=1, pv=2, pvb=1, start="2015-01-01 00", end="2015-01-01 09",
+                    dt=2, horizon=4, action_horizon=4, seed=7, record_t=range(0, 18), sub_steps=12,
+                    rp=[round(0.11 * np.sin(0.5 * k) - 0.04, 4) for k in range(8)]),
 }
 
 # the reference config.toml of every scenario (str.format fields: n, batt, pv, pvb, start, end, seed,
 # dt, action_horizon, horizon); shared with the tests, which build the same configs
 with open(os.path.join(HERE, "config_template.toml")) as _f:
     CONFIG_TMPL = _f.read()
+SUB_STEPS_LINE = "sub_subhourly_steps = 6\n"
+assert CONFIG_TMPL.count(SUB_STEPS_LINE) == 1
 
+
+def config_text(sc):
+    """The scenario's config.toml: the template, with its sub_subhourly_steps line replaced where
+    the scenario carries "sub_steps" (tests/fixtures.py config_text does the same)."""
+    text = CONFIG_TMPL.format(**sc)
+    if "sub_steps" in sc:
+        text = text.replace(SUB_STEPS_LINE, f"sub_subhourly_steps = {int(sc['sub_steps'])}\n")
+    return text
 
 
 class _NoiseRandom:
@@ -110,7 +137,7 @@ def run(name, sc, hook=None):
     data = os.path.join(work, "data")
     os.makedirs(data)
     with open(os.path.join(data, "config.toml"), "w") as f:
-        f.write(CONFIG_TMPL.format(**sc))
+        f.write(config_text(sc))
     os.symlink(os.path.join(REF, "dragg/data/nsrdb.csv"), os.path.join(data, "nsrdb.csv"))
     os.symlink(os.path.join(REF, "dragg/data/waterdraw_profiles.csv"),
                os.path.join(data, "waterdraw_profiles.csv"))

@@ -144,7 +144,7 @@ def test_lp_trajectories(solved):
         if rel["status"][i] != L.ST_OPTIMAL or "lp" not in r:
             continue
         lp = r["lp"]
-        S = 6
+        S = rel["b"].S                   # sub_subhourly_steps of the fixture (mpc_calc.py:503-505)
         pairs = [("temp_in_ev_opt", np.array(lp["temp_in_ev"][1:])),
                  ("temp_wh_ev_opt", np.array(lp["temp_wh_ev"][1:])),
                  ("hvac_heat_on_opt", np.array(lp["hvac_heat_on"]) / S),
@@ -288,7 +288,7 @@ def test_battery_lp_exact(solved):
         if rel["status"][i] != L.ST_OPTIMAL or rnd["status"][i] != L.ST_OPTIMAL or r["E0"] is None:
             continue
         H = rel["fc"].shape[1]
-        w = 0.92 ** np.arange(H) * np.array(r["total_price"][:H]) * 6
+        w = 0.92 ** np.arange(H) * np.array(r["total_price"][:H]) * rel["b"].S
         c_rel = float(w @ (rel["fc"][ich, :, i] + rel["fc"][idis, :, i]))
         c_rnd = float(w @ (rnd["fc"][ich, :, i] + rnd["fc"][idis, :, i]))
         assert abs(c_rel - c_rnd) <= 1e-9 * max(1.0, abs(c_rel)), (name, i, c_rel, c_rnd)

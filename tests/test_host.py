@@ -100,6 +100,27 @@ def test_pack_homes_matches_reference_constants():
         assert np.array_equal(draws[:len(hc.draw_sizes), i], hc.draw_sizes)
 
 
+def test_pack_homes_divides_by_sub_steps():
+    """sub_subhourly_steps = 4 (mpc_calc.py:159-162): the per-duty-unit powers are p / 4, bit for bit,
+    and a community whose homes disagree on S is refused (one batch has one dims.sub_steps; the
+    reference's responsive_hems share one hems table, aggregator.py:381-387, 446)."""
+    from dragg_amd import _lib as L
+    from dragg_amd.community import synthetic_homes
+    from dragg_amd.mpc import hems_dims, pack_homes
+    homes = synthetic_homes(8, seed=3, dt=4, horizon_hours=3, sub_steps=4)
+    homes[2]["hvac"]["p_c"], homes[2]["hvac"]["p_h"], homes[2]["wh"]["p"] = 3.7, 4.1, 2.3   # (not all 3.5 / 2.5)
+    P, _, _, dm = pack_homes(homes)
+    assert (dm["S"], dm["dt"], dm["H"]) == (4, 4, 12) and hems_dims(homes[0])[0] == 4
+    for i, h in enumerate(homes):
+        assert P[L.P["PC"], i] == float(h["hvac"]["p_c"]) / 4
+        assert P[L.P["PH"], i] == float(h["hvac"]["p_h"]) / 4
+        assert P[L.P["PW"], i] == float(h["wh"]["p"]) / 4
+    assert P[L.P["PC"], 2] == 0.925 and P[L.P["PH"], 2] == 1.025 and P[L.P["PW"], 2] == 0.575
+    homes[5]["hems"]["sub_subhourly_steps"] = 6
+    with pytest.raises(ValueError, match="share the hems settings"):
+        pack_homes(homes)
+
+
 def philox_np(ctr, key):
     """Philox4x32-10 in numpy (uint64 arithmetic), the generator of the device season noise."""
     c = [np.uint64(x) for x in ctr]

@@ -71,6 +71,10 @@ def test_run_dir_and_checkpoints(tmp_path):
     rd = R.run_dir("outputs", datetime(2015, 1, 1), datetime(2015, 1, 2), "all", 20, 6, 15, 6, "GLPK_MI", "golden")
     assert rd == ("outputs/2015-01-01T00_2015-01-02T00/all-homes_20-horizon_6-interval_15-2-solver_GLPK_MI/"
                   "version-golden")
+    # sub_subhourly_steps = 4 at 15-minute steps: interval_<60 // dt>-<(60 // dt) // S> (aggregator.py:825)
+    rd = R.run_dir("outputs", datetime(2015, 1, 1), datetime(2015, 1, 2), "all", 8, 4, 60 // 4, 4, "GLPK_MI", "golden")
+    assert rd == ("outputs/2015-01-01T00_2015-01-02T00/all-homes_8-horizon_4-interval_15-3-solver_GLPK_MI/"
+                  "version-golden")
     assert [R.checkpoint_interval(s, 4) for s in ("hourly", "daily", "weekly", "never")] == [4, 96, 672, 500]
     path = R.write_results(str(tmp_path), "baseline", {"a": [1.0], "Summary": {"TOU": ([0.07],)}})
     with open(path) as f:
