@@ -4901,7 +4901,7 @@ __global__ __launch_bounds__(WAVE, 2) void side_front_kernel(KArgs a) {
     __shared__ int take;
     for (int j = blockIdx.x; j < cnt;) {
         const int home = list[j] & HOME_MASK;
-        if (home < N) solve_direct<false, DM_FRONT, 1, 3>(a, home, smem, blockIdx.x, 0, 0);
+        if (home < N) solve_direct<PM_STEP, DM_FRONT, 1, 3>(a, home, smem, blockIdx.x, 0, 0);
         __syncthreads();
         if (threadIdx.x == 0) take = (int)gridDim.x + atomicAdd(list + N + 1, 1);
         __syncthreads();
@@ -5013,6 +5013,12 @@ __global__ void noise_kernel(int N, int H, uint64_t seed, int off, int stride, i
     if (2 * pr + 1 < H) out[(size_t)(2 * pr + 1) * N + home] = z1;
 }
 
+// --------------------------------------------------------------------------------------
+// Host layer.  Sizes and check_dims; the knobs; one description per launch (struct Launch: kernel,
+// threads, LDS) run through `run`, which raises the kernel's LDS limit once per device; the launch
+// sequences (launch: the serial step, launch_lag: one pass of a lag-mode step, both ending in
+// launch_deferred); the shared argument check (solve_args); the C ABI.
+// --------------------------------------------------------------------------------------
 bool direct_mode(const dragg_mpc_dims* d) { return d->int_mode == DRAGG_INT_ROUND || d->int_mode == DRAGG_INT_FAIL; }
 
 size_t workspace_bytes(const dragg_mpc_dims* d) {
@@ -5028,6 +5034,10 @@ size_t kernel_lds_bytes(const dragg_mpc_dims* d) {
     return direct_mode(d) ? (size_t)front_layout(d->horizon).bytes : (size_t)lds_doubles(d->horizon) * 8;
 }
 
+// the dynamic LDS limit the launches raise: the 160 KB of a CU less room for the kernels' static
+// LDS (the persistent launches' take slot)
+constexpr int LDS_DYN_MAX = 160 * 1024 - 256;
+
 int check_dims(const dragg_mpc_dims* d) {
     if (!d || d->n_homes < 0 || d->horizon < 1 || d->sub_steps < 1 || d->dt < 1) return DRAGG_E_ARG;
     if (d->n_homes > HOME_MASK) return DRAGG_E_ARG;                   // the deferred lists' home field
@@ -5036,32 +5046,17 @@ int check_dims(const dragg_mpc_dims* d) {
     if (d->n_groups < 0 || (d->n_groups > 1 && d->n_homes % d->n_groups != 0)) return DRAGG_E_ARG;
     if (direct_mode(d) && d->sub_steps > 15) return DRAGG_E_ARG;     // 4-bit duty in the DP record
     if (direct_mode(d) && !direct_fits(d->horizon)) return DRAGG_E_HORIZON;
-    if (kernel_lds_bytes(d) > 160 * 1024 - 256) return DRAGG_E_HORIZON;
-    if (direct_mode(d) && big_layout(d->horizon, d->sub_steps).bytes > 160 * 1024 - 256) return DRAGG_E_HORIZON;
-    if (direct_mode(d) && narrow_layout(d->horizon, d->sub_steps).bytes > 160 * 1024 - 256) return DRAGG_E_HORIZON;
+    if (kernel_lds_bytes(d) > LDS_DYN_MAX) return DRAGG_E_HORIZON;
+    if (direct_mode(d) && big_layout(d->horizon, d->sub_steps).bytes > LDS_DYN_MAX) return DRAGG_E_HORIZON;
+    if (direct_mode(d) && narrow_layout(d->horizon, d->sub_steps).bytes > LDS_DYN_MAX) return DRAGG_E_HORIZON;
     return DRAGG_OK;
 }
 
-// the dynamic LDS limit the launches raise: the 160 KB of a CU less room for the kernels' static
-// LDS (the persistent launches' take slot)
-constexpr int LDS_DYN_MAX = 160 * 1024 - 256;
-
-template <typename K>
-int launch_kernel(K kern, int& attr_state, const KArgs& a, int blocks, int nt, size_t lds, hipStream_t s) {
-    if (!attr_state) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX) !=
-            hipSuccess)
-            return DRAGG_E_LDS;
-        attr_state = 1;
-    }
-    if (a.d.n_homes == 0) return DRAGG_OK;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, s, a);
-    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
-}
-
-// hipFuncSetAttribute is per device: the attribute state is kept per device (a process driving
-// several GPUs sets it once on each)
+// devices a process may drive (the per-device state below: attributes, CU counts, occupancies)
 constexpr int MAX_DEV = 64;
+int current_device(int* dev) {
+    return hipGetDevice(dev) == hipSuccess && *dev >= 0 && *dev < MAX_DEV ? DRAGG_OK : DRAGG_E_HIP;
+}
 
 // Diagnostic knobs, read once per process (not on every step): DRAGG_WAVES_PER_HOME=1|2|4 forces
 // the hot launch's waves per home (A/B runs); DRAGG_FORCE_STEP_DP=1 sends every home's chains to
@@ -5100,12 +5095,6 @@ Knobs read_knobs() {
 Knobs g_knobs = read_knobs();          // at library load; again only on dragg_mpc_reload_knobs()
 const Knobs& knobs() { return g_knobs; }
 
-// Waves per home of the hot launch: one (measured at 1,250 homes, the 8-GPU shard of the bench:
-// 0.495 / 0.53 / 0.80 ms per step at 1 / 2 / 4 waves per home -- a stage's fixed latency (ranges,
-// scans, barriers) dominates its passes at these front sizes, so extra waves only add barriers);
-// DRAGG_WAVES_PER_HOME forces 2 or 4 (bit-identical results).
-int hot_waves() { return knobs().waves; }
-
 // Chunks per front-DP pass of the one-wave hot launch: two when the homes fit in two waves per SIMD
 // (N <= 8 per CU: the launch then lasts as long as its slowest home, whose LDS round trips the second
 // chunk overlaps), else one (three waves per SIMD hide them; the second chunk's registers would cost one)
@@ -5119,22 +5108,86 @@ int hot_ilp(int dev, int N) {
     return N <= 8 * cus[dev] ? 2 : 1;
 }
 
-// blocks of the persistent mid launch: as many as the GPU holds at once at its LDS (<= MID_SLOTS_MAX),
-// cached per (device, LDS bytes): a batch with another horizon gets its own occupancy
+// The launches of a step, each described once: its kernel (the PM instantiation), its threads per block and
+// its dynamic LDS bytes, from the dims and the knobs.  The serial step, both lag passes, mid_slots and
+// dragg_mpc_kernel_info_get all read them here.
+struct Launch { const void* kern; int nt; size_t lds; };
+struct Launches {
+    Launch home;          // relax / round_lp: the whole solve, one workgroup per home
+    Launch hot;           // round / fail: one block per home
+    Launch side_hot;      // the side pass's hot launch: persistent blocks over lag->skipped (a PM_STEP kernel)
+    // RL prices possible (a reward-price list): the cell bound of the deferred homes' indoor-air chains
+    // (explicit inputs carry no price list: their cell kernel is the step's)
+    Launch cell;
+    // the deferred homes: the mid launch (fronts of 384 labels, many blocks), its overflows to the
+    // big launch (2,048 labels, 2 blocks per CU), what no front DP can take to the step-function DP
+    Launch mid, big, narrow;
+};
+// nw, waves per home of the hot launch: one (measured at 1,250 homes, the 8-GPU shard of the bench:
+// 0.495 / 0.53 / 0.80 ms per step at 1 / 2 / 4 waves per home -- a stage's fixed latency (ranges,
+// scans, barriers) dominates its passes at these front sizes, so extra waves only add barriers);
+// DRAGG_WAVES_PER_HOME forces 2 or 4 (bit-identical results).  ilp: the one-wave kernel's chunks per pass (hot_ilp)
 template <int PM>
-int mid_slots(int dev, int H, int S) {
+Launches launches(const dragg_mpc_dims& d, int nw = 1, int ilp = 1) {
+    const int H = d.horizon, S = d.sub_steps;
+    const size_t lds = kernel_lds_bytes(&d);
+    const void* const hot = nw == 4 ? (const void*)mpc_direct_kernel<PM, DM_FRONT, 4>
+                          : nw == 2 ? (const void*)mpc_direct_kernel<PM, DM_FRONT, 2>
+                          : ilp == 2 ? (const void*)mpc_direct_kernel<PM, DM_FRONT, 1, 2>
+                                     : (const void*)mpc_direct_kernel<PM, DM_FRONT, 1>;
+    return {{(const void*)mpc_home_kernel<PM>, WAVE, lds},
+            {hot, nw * WAVE, lds},
+            {(const void*)side_front_kernel, WAVE, lds},
+            {(const void*)cell_kernel<PM == PM_GROUPED ? PM_GROUPED : PM_STEP>, NT_CELL, (size_t)cell_lds_bytes(H)},
+            {(const void*)mpc_direct_kernel<PM, DM_MID, NW_MID>, NW_MID * WAVE, (size_t)mid_layout(H, S).bytes},
+            {(const void*)mpc_direct_kernel<PM, DM_BUCKET, NW_BIG>, NW_BIG * WAVE, (size_t)big_layout(H, S).bytes},
+            {(const void*)mpc_direct_kernel<PM, DM_NARROW, NT_STEPS / WAVE>, NT_STEPS,
+             (size_t)narrow_layout(H, S, knobs().narrow_lds).bytes}};
+}
+
+// Raise the kernel's dynamic LDS limit once per (device, kernel function): hipFuncSetAttribute is per
+// device, so the kernels it was raised for are remembered per device, by their address (a process driving
+// several GPUs sets it once on each; a full table reuses its last slot)
+bool raise_lds_limit(int dev, const void* kern) {
+    static const void* raised[MAX_DEV][48] = {};
+    const void** k = raised[dev];
+    while (*k && *k != kern && k < raised[dev] + 47) ++k;
+    if (*k != kern && hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX) != hipSuccess)
+        return false;
+    *k = kern;
+    return true;
+}
+
+// (every entry point returns before this on an empty batch: blocks >= 1)
+int run(const Launch& l, int dev, const KArgs& a, int blocks, hipStream_t s) {
+    if (!raise_lds_limit(dev, l.kern)) return DRAGG_E_LDS;
+    void* args[] = {const_cast<KArgs*>(&a)};
+    (void)hipLaunchKernel(l.kern, dim3(blocks), dim3(l.nt), args, l.lds, s);
+    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+}
+
+// each list's length and the persistent launch's take counter after it, in one tiny launch
+// (three 8-byte memsets cost three fills: ~13 us of a 0.49 ms step at 1,250 homes)
+int reset_lists(hipStream_t s, int* a, int* b, int* c, int* d) {
+    hipLaunchKernelGGL(reset_lists_kernel, dim3(1), dim3(WAVE), 0, s, a, b, c, d, nullptr);
+    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+}
+
+// blocks of the persistent mid launch: as many as the GPU holds at once at its LDS (<= MID_SLOTS_MAX),
+// cached per (device, LDS bytes): a batch with another horizon gets its own occupancy; and per PM, whose
+// kernels need not have the same occupancy
+template <int PM>
+int mid_slots(int dev, const Launch& mid) {
     constexpr int NC = 8;
     static int cache_lds[MAX_DEV][NC] = {};
     static int cache_slots[MAX_DEV][NC] = {};
-    const int lds = mid_layout(H, S).bytes;
+    const int lds = (int)mid.lds;
     for (int i = 0; i < NC; ++i)
         if (cache_lds[dev][i] == lds) return cache_slots[dev][i];
     hipDeviceProp_t prop{};
     int per_cu = 0;
-    const void* k = (const void*)mpc_direct_kernel<PM, DM_MID, NW_MID>;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-        hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, NW_MID * WAVE, (size_t)lds) != hipSuccess)
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess || !raise_lds_limit(dev, mid.kern) ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mid.kern, mid.nt, mid.lds) != hipSuccess)
         return SECOND_SLOTS;
     const int slots = max(1, min(MID_SLOTS_MAX, per_cu * prop.multiProcessorCount));
     for (int i = 0; i < NC; ++i)
@@ -5142,55 +5195,34 @@ int mid_slots(int dev, int H, int S) {
     return slots;
 }
 
+// The launches after the hot one, over the lists it filled, in their one order: cell (only when a
+// reward-price list makes RL prices possible), mid, big and -- narrow blocks > 0 -- the step-function DP.
+// Stops at the first error.
+int launch_deferred(const Launches& l, int dev, const KArgs& b, int cell, int mid, int big, int narrow, hipStream_t s) {
+    int rc = b.d.n_rp > 1 ? run(l.cell, dev, b, cell, s) : DRAGG_OK;
+    if (!rc) rc = run(l.mid, dev, b, mid, s);
+    if (!rc) rc = run(l.big, dev, b, big, s);
+    if (!rc && narrow > 0) rc = run(l.narrow, dev, b, narrow, s);
+    return rc;
+}
+
+// The serial step (dragg_mpc_step, dragg_mpc_solve_explicit): the lists start empty, then the hot launch
+// over every home, then the deferred homes' launches at their full size
 template <int PM>
 int launch(const KArgs& a, hipStream_t s) {
-    static int attr_dev[MAX_DEV][10] = {};
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return DRAGG_E_HIP;
-    int* const attr = attr_dev[dev];
-    const int N = a.d.n_homes;
-    if (!direct_mode(&a.d)) return launch_kernel(mpc_home_kernel<PM>, attr[0], a, N, 64, kernel_lds_bytes(&a.d), s);
-    if (N == 0) return DRAGG_OK;
-    // the deferred list starts empty (its length word), then the hot launch, then the second
+    if (int rc = current_device(&dev)) return rc;
+    const int N = a.d.n_homes, H = a.d.horizon;
+    if (!direct_mode(&a.d)) return run(launches<PM>(a.d).home, dev, a, N, s);
+    const Launches l = launches<PM>(a.d, knobs().waves, hot_ilp(dev, N));
     char* const wsb = reinterpret_cast<char*>(a.p.workspace);
-    int* const len = reinterpret_cast<int*>(wsb + defer_offset(N, a.d.horizon)) + N;
-    int* const nlen = reinterpret_cast<int*>(wsb + narrow_list_offset(N, a.d.horizon)) + N;
-    int* const blen = reinterpret_cast<int*>(wsb + mid_list_offset(N, a.d.horizon)) + N;
-    KArgs b = a;
-    b.force_steps = knobs().force_steps;
-    b.step_pool_cap = knobs().step_pool_cap;
-    b.step_work_cap = knobs().step_work_cap;
-    b.narrow_lds = knobs().narrow_lds;
-    // each list's length and the persistent launch's take counter after it, in one tiny launch
-    // (three 8-byte memsets cost three fills: ~13 us of a 0.49 ms step at 1,250 homes)
-    hipLaunchKernelGGL(reset_lists_kernel, dim3(1), dim3(WAVE), 0, s, len, nlen, blen, nullptr, nullptr);
-    if (hipGetLastError() != hipSuccess) return DRAGG_E_HIP;
-    const size_t lds = kernel_lds_bytes(&a.d);
-    const int nw = hot_waves();
-
-    const int rc = nw == 4 ? launch_kernel(mpc_direct_kernel<PM, DM_FRONT, 4>, attr[4], b, N, 4 * WAVE, lds, s)
-                 : nw == 2 ? launch_kernel(mpc_direct_kernel<PM, DM_FRONT, 2>, attr[3], b, N, 2 * WAVE, lds, s)
-                 : hot_ilp(dev, N) == 2 ? launch_kernel(mpc_direct_kernel<PM, DM_FRONT, 1, 2>, attr[8], b, N, WAVE, lds, s)
-                                        : launch_kernel(mpc_direct_kernel<PM, DM_FRONT, 1>, attr[1], b, N, WAVE, lds, s);
-    if (rc) return rc;
-    // RL prices possible (a reward-price list): the cell bound of the deferred homes' indoor-air chains
-    if (a.d.n_rp > 1) {
-        const int rcc = launch_kernel(cell_kernel<PM == PM_GROUPED ? PM_GROUPED : PM_STEP>, attr[7], b, min(N, CELL_BLOCKS), NT_CELL,
-                                      (size_t)cell_lds_bytes(a.d.horizon), s);
-        if (rcc) return rcc;
-    }
-    // the deferred homes: the mid launch (fronts of 384 labels, many blocks), its overflows to the
-    // big launch (2,048 labels, 2 blocks per CU), what no front DP can take to the step-function DP
-    const int rcm = launch_kernel(mpc_direct_kernel<PM, DM_MID, NW_MID>, attr[6], b,
-                                  min(N, mid_slots<PM>(dev, a.d.horizon, a.d.sub_steps)), NW_MID * WAVE,
-                                  (size_t)mid_layout(a.d.horizon, a.d.sub_steps).bytes, s);
-    if (rcm) return rcm;
-    const int rc2 = launch_kernel(mpc_direct_kernel<PM, DM_BUCKET, NW_BIG>, attr[2], b, min(N, SECOND_SLOTS),
-                                  NW_BIG * WAVE, (size_t)big_layout(a.d.horizon, a.d.sub_steps).bytes, s);
-    if (rc2) return rc2;
-    const int rcn = launch_kernel(mpc_direct_kernel<PM, DM_NARROW, NT_STEPS / WAVE>, attr[5], b, min(N, NARROW_SLOTS),
-                                  NT_STEPS, (size_t)narrow_layout(a.d.horizon, a.d.sub_steps, b.narrow_lds).bytes, s);
-    return rcn;
+    int* const len = reinterpret_cast<int*>(wsb + defer_offset(N, H)) + N;
+    int* const nlen = reinterpret_cast<int*>(wsb + narrow_list_offset(N, H)) + N;
+    int* const blen = reinterpret_cast<int*>(wsb + mid_list_offset(N, H)) + N;
+    if (int rc = reset_lists(s, len, nlen, blen, nullptr)) return rc;
+    if (int rc = run(l.hot, dev, a, N, s)) return rc;
+    return launch_deferred(l, dev, a, min(N, CELL_BLOCKS), min(N, mid_slots<PM>(dev, l.mid)), min(N, SECOND_SLOTS),
+                           min(N, NARROW_SLOTS), s);
 }
 
 // Lag mode: one timestep in two passes on two streams (the caller orders them: the side pass of step t
@@ -5207,76 +5239,75 @@ int launch(const KArgs& a, hipStream_t s) {
 // empty blocks run beside the main pass's next hot launch.  Measured (driver window, 20 steps): a full-
 // size side pass (256 / ~1,800 / 512 / 8 blocks) 1.482 ms/step, 16 / 16 / 16 / 2 blocks 1.434, 4 / 4 /
 // 4 / 1 1.435, serial steps 1.427; full day 1.807 / 1.759 / 1.775 ms/step
-constexpr int SIDE_HOT_BLOCKS = 16;         // persistent blocks of the side pass's hot launch
-constexpr int SIDE_MID_BLOCKS = 16;         // ... mid launch
-constexpr int SIDE_BIG_BLOCKS = 16;         // ... big launch
-constexpr int SIDE_NARROW_BLOCKS = 2;       // ... step-function launch (each needs a whole CU's LDS)
-// blocks of one side-pass launch: the DRAGG_SIDE_GRID entry (knob > 0) or the default, at most one per home
-// and at most `slots` (the launch's per-block scratch regions), at least one
-int side_grid_blocks(int knob, int dflt, int N, int slots) { return max(1, min(min(N, slots), knob > 0 ? knob : dflt)); }
+// persistent blocks of the side pass's hot, mid, big and step-function launches (each of the last needs a
+// whole CU's LDS)
+constexpr int SIDE_BLOCKS[4] = {16, 16, 16, 2};
+// blocks of each side-pass launch: the DRAGG_SIDE_GRID entry (knob > 0) or the default, at most one per home
+// and at most `cap` (the launch's per-block scratch regions), at least one
 void side_grids(int N, int out[4]) {
     const int* sg = knobs().side_grid;
     const int cap[4] = {N, MID_SLOTS_MAX, SECOND_SLOTS, narrow_slots(N)};
-    const int dflt[4] = {SIDE_HOT_BLOCKS, SIDE_MID_BLOCKS, SIDE_BIG_BLOCKS, SIDE_NARROW_BLOCKS};
-    for (int i = 0; i < 4; ++i) out[i] = side_grid_blocks(sg[i], dflt[i], N, cap[i]);
+    for (int i = 0; i < 4; ++i) out[i] = max(1, min(min(N, cap[i]), sg[i] > 0 ? sg[i] : SIDE_BLOCKS[i]));
 }
+// One pass of a lag-mode step (PM_STEP kernels; the lists and per-block scratch are a.lws's): a hot launch,
+// then launch_deferred -- the main pass at full size without the step-function launch, the side pass on
+// the side_grids blocks with it
 int launch_lag(const KArgs& a, bool side, hipStream_t s) {
-    static int attr_dev[MAX_DEV][10] = {};
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return DRAGG_E_HIP;
-    int* const attr = attr_dev[dev];
+    if (int rc = current_device(&dev)) return rc;
     const int N = a.d.n_homes, H = a.d.horizon;
-    if (N == 0) return DRAGG_OK;
-    char* const lw = a.lws;
-    int* const len = reinterpret_cast<int*>(lw + defer_offset(N, H)) + N;
-    int* const blen = reinterpret_cast<int*>(lw + mid_list_offset(N, H)) + N;
-    KArgs b = a;
+    const Launches l = launches<PM_STEP>(a.d, 1, hot_ilp(dev, N));
+    int* const len = reinterpret_cast<int*>(a.lws + defer_offset(N, H)) + N;
+    int* const blen = reinterpret_cast<int*>(a.lws + mid_list_offset(N, H)) + N;
     // DRAGG_FORCE_STEP_DP holds here too: the hot launches list every home's chains in the step's narrow
     // list (lag->narrow), which the side pass's step-function launch then solves.  (DRAGG_WAVES_PER_HOME
     // does not: both passes run the one-wave hot kernel; the header says so.)
-    b.force_steps = knobs().force_steps;
-    b.step_pool_cap = knobs().step_pool_cap;
-    b.step_work_cap = knobs().step_work_cap;
-    b.narrow_lds = knobs().narrow_lds;
-    const size_t lds = kernel_lds_bytes(&a.d);
-    if (!side) {
-        hipLaunchKernelGGL(reset_lists_kernel, dim3(1), dim3(WAVE), 0, s, len, blen, a.skip + N, a.nar + N, nullptr);
-        if (hipGetLastError() != hipSuccess) return DRAGG_E_HIP;
-        b.hot_list = nullptr;
-        b.side = 0;
-        int rc = hot_ilp(dev, N) == 2 ? launch_kernel(mpc_direct_kernel<false, DM_FRONT, 1, 2>, attr[8], b, N, WAVE, lds, s)
-                                      : launch_kernel(mpc_direct_kernel<false, DM_FRONT, 1>, attr[1], b, N, WAVE, lds, s);
-        if (!rc && a.d.n_rp > 1)
-            rc = launch_kernel(cell_kernel<PM_STEP>, attr[7], b, min(N, CELL_BLOCKS), NT_CELL, (size_t)cell_lds_bytes(H), s);
-        if (!rc) rc = launch_kernel(mpc_direct_kernel<false, DM_MID, NW_MID>, attr[6], b,
-                                    min(N, mid_slots<false>(dev, H, a.d.sub_steps)), NW_MID * WAVE,
-                                    (size_t)mid_layout(H, a.d.sub_steps).bytes, s);
-        if (!rc) rc = launch_kernel(mpc_direct_kernel<false, DM_BUCKET, NW_BIG>, attr[2], b, min(N, SECOND_SLOTS),
-                                    NW_BIG * WAVE, (size_t)big_layout(H, a.d.sub_steps).bytes, s);
-        return rc;
+    if (!side) {        // (hot_list NULL and side 0, as solve_args left them)
+        if (int rc = reset_lists(s, len, blen, a.skip + N, a.nar + N)) return rc;
+        if (int rc = run(l.hot, dev, a, N, s)) return rc;
+        return launch_deferred(l, dev, a, min(N, CELL_BLOCKS), min(N, mid_slots<PM_STEP>(dev, l.mid)),
+                               min(N, SECOND_SLOTS), 0, s);
     }
     // (lag->skipped and lag->narrow were zeroed by the main pass, which filled them)
-    hipLaunchKernelGGL(reset_lists_kernel, dim3(1), dim3(WAVE), 0, s, len, blen, nullptr, nullptr, nullptr);
-    if (hipGetLastError() != hipSuccess) return DRAGG_E_HIP;
-    b.hot_list = a.skip;
-    b.skip = nullptr;
-    b.side = 1;
+    if (int rc = reset_lists(s, len, blen, nullptr, nullptr)) return rc;
     // the persistent launches index per-block scratch by blockIdx.x: a DRAGG_SIDE_GRID entry is clamped to
     // its region's slots (the mid launch's MID_SLOTS_MAX rows, the big launch's SECOND_SLOTS, the
     // step-function launch's narrow_slots(N) pools; the hot and cell launches keep no per-block scratch)
     int grid[4];
     side_grids(N, grid);
-    int rc = launch_kernel(side_front_kernel, attr[0], b, grid[0], WAVE, lds, s);
+    KArgs b = a;
+    b.side = 1;
+    b.skip = nullptr;
+    b.hot_list = a.skip;
+    if (int rc = run(l.side_hot, dev, b, grid[0], s)) return rc;
     b.hot_list = nullptr;
-    if (!rc && a.d.n_rp > 1)
-        rc = launch_kernel(cell_kernel<PM_STEP>, attr[7], b, grid[1], NT_CELL, (size_t)cell_lds_bytes(H), s);
-    if (!rc) rc = launch_kernel(mpc_direct_kernel<false, DM_MID, NW_MID>, attr[6], b, grid[1], NW_MID * WAVE,
-                                (size_t)mid_layout(H, a.d.sub_steps).bytes, s);
-    if (!rc) rc = launch_kernel(mpc_direct_kernel<false, DM_BUCKET, NW_BIG>, attr[2], b, grid[2],
-                                NW_BIG * WAVE, (size_t)big_layout(H, a.d.sub_steps).bytes, s);
-    if (!rc) rc = launch_kernel(mpc_direct_kernel<false, DM_NARROW, NT_STEPS / WAVE>, attr[5], b,
-                                grid[3], NT_STEPS, (size_t)narrow_layout(H, a.d.sub_steps, b.narrow_lds).bytes, s);
-    return rc;
+    return launch_deferred(l, dev, b, grid[1], grid[1], grid[2], grid[3], s);
+}
+
+// The argument check the solve entries share, then their kernel arguments with the knobs applied; each
+// entry adds only what is its own.  env: the step reads the environment lists (not so with explicit
+// inputs).  DRAGG_OK for an empty batch too (*a is not filled): the caller returns on it.
+int solve_args(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, const dragg_mpc_hash* hash,
+               const dragg_mpc_out* out, int32_t timestep, bool env, KArgs* a) {
+    const int rc = check_dims(dims);
+    if (rc) return rc;
+    if (!prob || !hash || !out || timestep < 0) return DRAGG_E_ARG;
+    // an empty shard (more ranks than homes) is a no-op; its per-home arrays may be NULL
+    if (dims->n_homes == 0) return DRAGG_OK;
+    if (!prob->params || !prob->home_type || !hash->vals || !hash->fc || !out->status || !out->iters || !out->obj ||
+        !out->relax_obj || (direct_mode(dims) && !prob->workspace))
+        return DRAGG_E_ARG;
+    if (env && (!prob->oat || !prob->ghi || !prob->tou || !prob->reward_price || !prob->draw_hourly)) return DRAGG_E_ARG;
+    if (env && dims->n_rp != 1 && dims->n_rp < dims->horizon) return DRAGG_E_ARG;   // numpy broadcast error
+    if (env && prob->start_index + timestep + dims->horizon >= dims->n_env) return DRAGG_E_ARG;
+    *a = KArgs{};
+    a->d = *dims; a->p = *prob; a->vals = hash->vals; a->fc = hash->fc; a->out = *out; a->t = timestep;
+    // the diagnostic knobs, for every path (only the direct-mode kernels read them)
+    a->force_steps = knobs().force_steps;
+    a->step_pool_cap = knobs().step_pool_cap;
+    a->step_work_cap = knobs().step_work_cap;
+    a->narrow_lds = knobs().narrow_lds;
+    return DRAGG_OK;
 }
 
 }  // namespace
@@ -5328,64 +5359,41 @@ int dragg_mpc_lds_bytes(const dragg_mpc_dims* dims) {
 
 int dragg_mpc_step(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, dragg_mpc_hash* hash,
                    dragg_mpc_out* out, int32_t timestep, const double* noise, void* stream) {
-    int rc = check_dims(dims);
-    if (rc) return rc;
-    // an empty shard (more ranks than homes) is a no-op; its per-home arrays may be NULL
-    if (dims->n_homes == 0) return (prob && hash && out && timestep >= 0) ? DRAGG_OK : DRAGG_E_ARG;
-    if (!prob || !hash || !out || timestep < 0 || !prob->params || !prob->home_type || !prob->oat ||
-        !prob->ghi || !prob->tou || !prob->reward_price || !prob->draw_hourly || !hash->vals || !hash->fc ||
-        !out->status || !out->iters || !out->obj || !out->relax_obj)
-        return DRAGG_E_ARG;
-    if (dims->n_rp != 1 && dims->n_rp < dims->horizon) return DRAGG_E_ARG;   // numpy broadcast error
-    if (prob->start_index + timestep + dims->horizon >= dims->n_env) return DRAGG_E_ARG;
-    if (direct_mode(dims) && !prob->workspace) return DRAGG_E_ARG;
-    KArgs a{};
-    a.d = *dims; a.p = *prob; a.vals = hash->vals; a.fc = hash->fc; a.out = *out; a.noise = noise;
-    a.t = timestep;
+    KArgs a;
+    const int rc = solve_args(dims, prob, hash, out, timestep, true, &a);
+    if (rc || dims->n_homes == 0) return rc;
+    a.noise = noise;
     // (a grouped batch runs the kernels instantiated with the grouped prologue: an ordinary step's are untouched)
     return a.d.n_groups > 1 ? launch<PM_GROUPED>(a, (hipStream_t)stream) : launch<PM_STEP>(a, (hipStream_t)stream);
 }
 
-static int lag_args(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, dragg_mpc_hash* hash,
-                    dragg_mpc_out* out, int32_t timestep, const dragg_mpc_lag* lag, bool side, KArgs* a) {
-    int rc = check_dims(dims);
+// one pass of a lag-mode step: solve_args, then what only lag mode needs
+static int step_lag(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, dragg_mpc_hash* hash,
+                    dragg_mpc_out* out, int32_t timestep, const dragg_mpc_lag* lag, bool side, void* stream) {
+    KArgs a;
+    const int rc = solve_args(dims, prob, hash, out, timestep, true, &a);
     if (rc) return rc;
-    if (!direct_mode(dims) || !lag || !prob || !hash || !out || timestep < 0) return DRAGG_E_ARG;
-    if (dims->n_groups > 1) return DRAGG_E_ARG;                       // grouped batches: dragg_mpc_step only
+    if (!direct_mode(dims) || !lag || dims->n_groups > 1) return DRAGG_E_ARG;   // (grouped batches: dragg_mpc_step only)
     if (dims->n_homes == 0) return DRAGG_OK;
-    if (!lag->clock || !lag->skipped || !lag->narrow || (side && !lag->side_workspace) || !prob->params ||
-        !prob->home_type || !prob->oat || !prob->ghi || !prob->tou || !prob->reward_price || !prob->draw_hourly ||
-        !prob->workspace || !hash->vals || !hash->fc || !out->status || !out->iters || !out->obj || !out->relax_obj)
-        return DRAGG_E_ARG;
-    if (dims->n_rp != 1 && dims->n_rp < dims->horizon) return DRAGG_E_ARG;
-    if (prob->start_index + timestep + dims->horizon >= dims->n_env) return DRAGG_E_ARG;
+    if (!lag->clock || !lag->skipped || !lag->narrow || (side && !lag->side_workspace)) return DRAGG_E_ARG;
     if (timestep >= LAG_SIDE - 1) return DRAGG_E_ARG;
-    *a = KArgs{};
-    a->d = *dims; a->p = *prob; a->vals = hash->vals; a->fc = hash->fc; a->out = *out; a->noise = nullptr;
-    a->t = timestep;
     // the side workspace holds only the span [defer_offset, w_region_offset) of the layout: its base stands
     // at defer_offset (the kernels address lists and per-block scratch as lws + their layout offset, all
     // inside that span; nothing below defer_offset is addressed through lws)
-    a->lws = side ? reinterpret_cast<char*>(lag->side_workspace) - defer_offset(dims->n_homes, dims->horizon)
-                  : reinterpret_cast<char*>(prob->workspace);
-    a->clk = lag->clock; a->skip = lag->skipped; a->nar = lag->narrow;
-    return DRAGG_OK;
+    a.lws = side ? reinterpret_cast<char*>(lag->side_workspace) - defer_offset(dims->n_homes, dims->horizon)
+                 : reinterpret_cast<char*>(prob->workspace);
+    a.clk = lag->clock; a.skip = lag->skipped; a.nar = lag->narrow;
+    return launch_lag(a, side, (hipStream_t)stream);
 }
 
 int dragg_mpc_step_main(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, dragg_mpc_hash* hash,
                         dragg_mpc_out* out, int32_t timestep, const dragg_mpc_lag* lag, void* stream) {
-    KArgs a;
-    const int rc = lag_args(dims, prob, hash, out, timestep, lag, false, &a);
-    if (rc || dims->n_homes == 0) return rc;
-    return launch_lag(a, false, (hipStream_t)stream);
+    return step_lag(dims, prob, hash, out, timestep, lag, false, stream);
 }
 
 int dragg_mpc_step_side(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, dragg_mpc_hash* hash,
                         dragg_mpc_out* out, int32_t timestep, const dragg_mpc_lag* lag, void* stream) {
-    KArgs a;
-    const int rc = lag_args(dims, prob, hash, out, timestep, lag, true, &a);
-    if (rc || dims->n_homes == 0) return rc;
-    return launch_lag(a, true, (hipStream_t)stream);
+    return step_lag(dims, prob, hash, out, timestep, lag, true, stream);
 }
 
 int dragg_mpc_lag_reset(const dragg_mpc_dims* dims, const dragg_mpc_lag* lag, int32_t timestep, void* stream) {
@@ -5411,18 +5419,15 @@ int dragg_mpc_aggregate_rows(const dragg_mpc_dims* dims, const double* rows, int
 int dragg_mpc_solve_explicit(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob,
                              const dragg_mpc_explicit* in, dragg_mpc_hash* hash, dragg_mpc_out* out,
                              void* stream) {
-    int rc = check_dims(dims);
+    KArgs a;
+    const int rc = solve_args(dims, prob, hash, out, 0, false, &a);
     if (rc) return rc;
-    if (dims->n_groups > 1) return DRAGG_E_ARG;                       // (explicit inputs carry no price list)
-    if (dims->n_homes == 0) return (prob && in && hash && out) ? DRAGG_OK : DRAGG_E_ARG;
-    if (!prob || !in || !hash || !out || !prob->params || !prob->home_type || !in->t || !in->T0 ||
-        !in->Tw0 || !in->E0 || !in->counter || !in->winter || !in->draw || !in->oat || !in->ghi ||
-        !in->price || !hash->vals || !hash->fc || !out->status || !out->iters || !out->obj ||
-        !out->relax_obj)
+    if (!in || dims->n_groups > 1) return DRAGG_E_ARG;                // (explicit inputs carry no price list)
+    if (dims->n_homes == 0) return DRAGG_OK;
+    if (!in->t || !in->T0 || !in->Tw0 || !in->E0 || !in->counter || !in->winter || !in->draw || !in->oat ||
+        !in->ghi || !in->price)
         return DRAGG_E_ARG;
-    if (direct_mode(dims) && !prob->workspace) return DRAGG_E_ARG;
-    KArgs a{};
-    a.d = *dims; a.p = *prob; a.ex = *in; a.vals = hash->vals; a.fc = hash->fc; a.out = *out;
+    a.ex = *in;
     return launch<PM_EXPLICIT>(a, (hipStream_t)stream);
 }
 
@@ -5433,30 +5438,28 @@ int dragg_mpc_kernel_info_get(const dragg_mpc_dims* dims, dragg_mpc_kernel_info*
     if (rc) return rc;
     if (!info) return DRAGG_E_ARG;
     *info = dragg_mpc_kernel_info{};
-    auto one = [&](const void* kern, int i, size_t lds, int nt) -> int {
+    auto one = [&](const Launch& l, int i) -> int {
         hipFuncAttributes fa{};
-        if (hipFuncGetAttributes(&fa, kern) != hipSuccess) return DRAGG_E_HIP;
-        // the launches raise the dynamic LDS limit first (launch_kernel); so does the query
-        if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX) != hipSuccess)
+        if (hipFuncGetAttributes(&fa, l.kern) != hipSuccess) return DRAGG_E_HIP;
+        // the launches raise the dynamic LDS limit first (run); so does the query
+        if (hipFuncSetAttribute(l.kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DYN_MAX) != hipSuccess)
             return DRAGG_E_LDS;
         int blocks = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kern, nt, lds) != hipSuccess) return DRAGG_E_HIP;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, l.kern, l.nt, l.lds) != hipSuccess) return DRAGG_E_HIP;
         info->vgprs[i] = fa.numRegs;
         info->scratch_bytes[i] = (int32_t)fa.localSizeBytes;
-        info->lds_bytes[i] = (int32_t)lds;
-        info->threads[i] = nt;
+        info->lds_bytes[i] = (int32_t)l.lds;
+        info->threads[i] = l.nt;
         info->blocks_per_cu[i] = blocks;
         return DRAGG_OK;
     };
-    if (!direct_mode(dims)) return one((const void*)mpc_home_kernel<false>, 0, kernel_lds_bytes(dims), WAVE);
-    const int H = dims->horizon, S = dims->sub_steps;
-    int r = one((const void*)mpc_direct_kernel<false, DM_FRONT>, 0, kernel_lds_bytes(dims), WAVE);
-    if (!r) r = one((const void*)mpc_direct_kernel<false, DM_BUCKET, NW_BIG>, 1, (size_t)big_layout(H, S).bytes,
-                    NW_BIG * WAVE);
-    if (!r) r = one((const void*)mpc_direct_kernel<false, DM_MID, NW_MID>, 2, (size_t)mid_layout(H, S).bytes,
-                    NW_MID * WAVE);
-    if (!r) r = one((const void*)mpc_direct_kernel<false, DM_NARROW, NT_STEPS / WAVE>, 3,
-                    (size_t)narrow_layout(H, S, knobs().narrow_lds).bytes, NT_STEPS);
+    // the kernels of an ordinary step: the one-wave hot kernel at one chunk per pass, then big, mid, narrow
+    const Launches l = launches<PM_STEP>(*dims);
+    if (!direct_mode(dims)) return one(l.home, 0);
+    int r = one(l.hot, 0);
+    if (!r) r = one(l.big, 1);
+    if (!r) r = one(l.mid, 2);
+    if (!r) r = one(l.narrow, 3);
     return r;
 }
 

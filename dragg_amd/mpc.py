@@ -246,10 +246,18 @@ class MPCBatch:
     def _hash(self):
         return L.Hash(vals=L.ptr(self.vals), fc=L.ptr(self.fc_store))
 
-    def _out(self, hist=None):
-        return L.Out(status=L.ptr(self.status), iters=L.ptr(self.iters), obj=L.ptr(self.obj),
-                     relax_obj=L.ptr(self.relax_obj), hist=L.ptr(hist), cycles=L.ptr(self.cycles),
-                     int_path=L.ptr(self.int_path))
+    def _out(self, hist=None, status=None, int_path=None, timed=True):
+        """The step's outputs: `status` / `int_path` rows of the caller's (default: the batch's own);
+        timed=False: no phase stamps."""
+        return L.Out(status=L.ptr(status if status is not None else self.status), iters=L.ptr(self.iters),
+                     obj=L.ptr(self.obj), relax_obj=L.ptr(self.relax_obj), hist=L.ptr(hist),
+                     cycles=L.ptr(self.cycles if timed else None),
+                     int_path=L.ptr(int_path if int_path is not None else self.int_path))
+
+    def _call(self, fn, *args, stream=None):
+        """One library call: the dims, `args` (a struct goes by reference: the argtypes of L.load),
+        the launch stream (default: the current one); a non-zero return code raises."""
+        L.check(fn(self.dims, *args, L.stream_ptr(stream, self.device)))
 
     def enable_phase_timing(self, on=True):
         """Stamp per-phase shader cycles of every home into self.cycles [NPHASE][N] (diagnostic)."""
@@ -262,7 +270,16 @@ class MPCBatch:
             self.drain(stream)
             if self.lag is not None:
                 self.lag["next"] = None          # the clocks no longer describe the state
-            return self._step(t, noise, hist, stream)
+            if noise is not None:
+                noise = noise.to(device=self.device, dtype=torch.float64)
+                if self.groups > 1 and tuple(noise.shape) == (self.H, self.Nb):
+                    noise = noise.repeat(1, self.groups)        # the base homes' draws, for every replica
+                noise = noise.contiguous()
+                assert tuple(noise.shape) == (self.H, self.N)
+            self._call(self.lib.dragg_mpc_step, self._problem(), self._hash(), self._out(hist), int(t), L.ptr(noise),
+                       stream=stream)
+            self._keep = (noise, hist)
+            return self.status
 
     # ------------------------------------------------------------------ lag mode
     def enable_lag(self, ring=128):
@@ -299,45 +316,35 @@ class MPCBatch:
         lagging home's later -- so they must be this step's own rows; nothing of the step may be read
         before drain().  `sums_row` ([3] f64, optional): collect_data's sums of the step, from `hist`,
         computed on the side stream after the step's side pass (dragg_mpc_aggregate_rows)."""
-        with torch.cuda.device(self.device):
-            return self._step_lagged(t, hist, status_row, stream, path_row, sums_row)
-
-    def _step_lagged(self, t, hist, status_row, stream, path_row=None, sums_row=None):
         lg = self.lag
         if lg is None:
             raise RuntimeError("enable_lag() first")
         assert hist is not None and status_row is not None and status_row.dtype == torch.int32
-        main = stream if stream is not None else torch.cuda.current_stream(self.device)
-        side = lg["stream"]
-        slot = t % lg["ring"]
-        lag = L.Lag(clock=L.ptr(lg["clock"]), skipped=L.ptr(lg["lists"][slot, 0]), narrow=L.ptr(lg["lists"][slot, 1]),
-                    side_workspace=L.ptr(lg["side_ws"]))
-        if lg["next"] != t:
-            # (the first lag-mode step, or one after a serial step: every step before t is complete)
-            self.drain(main)
-            L.check(self.lib.dragg_mpc_lag_reset(ctypes.byref(self.dims), ctypes.byref(lag), int(t),
-                                                  L.stream_ptr(main, self.device)))
-        if lg["recorded"][slot]:
-            main.wait_event(lg["side_done"][slot])      # the side pass of step t - ring is done with the lists
-        prob, hsh = self._problem(), self._hash()
-        out = L.Out(status=L.ptr(status_row), iters=L.ptr(self.iters), obj=L.ptr(self.obj),
-                    relax_obj=L.ptr(self.relax_obj), hist=L.ptr(hist), cycles=None,
-                    int_path=L.ptr(path_row if path_row is not None else self.int_path))
-        L.check(self.lib.dragg_mpc_step_main(ctypes.byref(self.dims), ctypes.byref(prob), ctypes.byref(hsh),
-                                             ctypes.byref(out), int(t), ctypes.byref(lag), L.stream_ptr(main, self.device)))
-        lg["main_done"].record(main)
-        side.wait_event(lg["main_done"])
-        L.check(self.lib.dragg_mpc_step_side(ctypes.byref(self.dims), ctypes.byref(prob), ctypes.byref(hsh),
-                                             ctypes.byref(out), int(t), ctypes.byref(lag), L.stream_ptr(side, self.device)))
-        if sums_row is not None:
-            L.check(self.lib.dragg_mpc_aggregate_rows(ctypes.byref(self.dims), L.ptr(hist), 1, L.ptr(sums_row),
-                                                      L.stream_ptr(side, self.device)))
-        lg["side_done"][slot].record(side)
-        lg["recorded"][slot] = True
-        lg["last"] = slot
-        lg["next"] = t + 1
-        lg["pending"] = True
-        self._keep = (hist, status_row, path_row, sums_row)
+        with torch.cuda.device(self.device):
+            main = stream if stream is not None else torch.cuda.current_stream(self.device)
+            side = lg["stream"]
+            slot = t % lg["ring"]
+            lag = L.Lag(clock=L.ptr(lg["clock"]), skipped=L.ptr(lg["lists"][slot, 0]),
+                        narrow=L.ptr(lg["lists"][slot, 1]), side_workspace=L.ptr(lg["side_ws"]))
+            if lg["next"] != t:
+                # (the first lag-mode step, or one after a serial step: every step before t is complete)
+                self.drain(main)
+                self._call(self.lib.dragg_mpc_lag_reset, lag, int(t), stream=main)
+            if lg["recorded"][slot]:
+                main.wait_event(lg["side_done"][slot])      # the side pass of step t - ring is done with the lists
+            step = (self._problem(), self._hash(), self._out(hist, status_row, path_row, timed=False), int(t), lag)
+            self._call(self.lib.dragg_mpc_step_main, *step, stream=main)
+            lg["main_done"].record(main)
+            side.wait_event(lg["main_done"])
+            self._call(self.lib.dragg_mpc_step_side, *step, stream=side)
+            if sums_row is not None:
+                self._call(self.lib.dragg_mpc_aggregate_rows, L.ptr(hist), 1, L.ptr(sums_row), stream=side)
+            lg["side_done"][slot].record(side)
+            lg["recorded"][slot] = True
+            lg["last"] = slot
+            lg["next"] = t + 1
+            lg["pending"] = True
+            self._keep = (hist, status_row, path_row, sums_row)
 
     def drain(self, stream=None):
         """Join the side stream into `stream` (default: the current one): after this, everything the
@@ -354,64 +361,38 @@ class MPCBatch:
         aggregate() on each row)."""
         with torch.cuda.device(self.device):
             out = torch.empty((rows.shape[0], 3), dtype=torch.float64, device=self.device)
-            L.check(self.lib.dragg_mpc_aggregate_rows(ctypes.byref(self.dims), L.ptr(rows.contiguous()),
-                                                      int(rows.shape[0]), L.ptr(out),
-                                                      L.stream_ptr(stream, self.device)))
+            self._call(self.lib.dragg_mpc_aggregate_rows, L.ptr(rows.contiguous()), int(rows.shape[0]), L.ptr(out),
+                       stream=stream)
             return out
-
-    def _step(self, t, noise, hist, stream):
-        if noise is not None:
-            noise = noise.to(device=self.device, dtype=torch.float64)
-            if self.groups > 1 and tuple(noise.shape) == (self.H, self.Nb):
-                noise = noise.repeat(1, self.groups)        # the base homes' draws, for every replica
-            noise = noise.contiguous()
-            assert tuple(noise.shape) == (self.H, self.N)
-        prob, hsh, out = self._problem(), self._hash(), self._out(hist)
-        L.check(self.lib.dragg_mpc_step(ctypes.byref(self.dims), ctypes.byref(prob), ctypes.byref(hsh),
-                                        ctypes.byref(out), int(t), L.ptr(noise), L.stream_ptr(stream, self.device)))
-        self._keep = (noise, hist)
-        return self.status
 
     def solve_explicit(self, t, T0, Tw0, E0, counter, winter, draw, oat, ghi, price, stream=None):
         """Independent per-home solves with explicit inputs ([N] and [H+1 or H][N] arrays)."""
-        with torch.cuda.device(self.device):
-            return self._solve_explicit(t, T0, Tw0, E0, counter, winter, draw, oat, ghi, price, stream)
-
-    def _solve_explicit(self, t, T0, Tw0, E0, counter, winter, draw, oat, ghi, price, stream):
-        self.drain(stream)
         dev, N, H = self.device, self.N, self.H
 
         def d(x, shape, dtype=torch.float64):
-            tt = torch.as_tensor(np.asarray(x), dtype=dtype).to(dev).reshape(shape).contiguous()
-            return tt
-        ex_t = {
-            "t": d(t, (N,), torch.int32), "T0": d(T0, (N,)), "Tw0": d(Tw0, (N,)),
-            "E0": d(np.nan_to_num(np.asarray(E0, dtype=float)), (N,)),
-            "counter": d(counter, (N,), torch.int32), "winter": d(winter, (N,), torch.int32),
-            "draw": d(draw, (H + 1, N)), "oat": d(oat, (H + 1, N)), "ghi": d(ghi, (H + 1, N)),
-            "price": d(price, (H, N)),
-        }
-        ex = L.Explicit(**{k: L.ptr(v) for k, v in ex_t.items()})
-        prob, hsh, out = self._problem(), self._hash(), self._out()
-        L.check(self.lib.dragg_mpc_solve_explicit(ctypes.byref(self.dims), ctypes.byref(prob), ctypes.byref(ex),
-                                                  ctypes.byref(hsh), ctypes.byref(out),
-                                                  L.stream_ptr(stream, self.device)))
-        self._keep = ex_t
-        return self.status
+            return torch.as_tensor(np.asarray(x), dtype=dtype).to(dev).reshape(shape).contiguous()
+        with torch.cuda.device(dev):
+            self.drain(stream)
+            ex_t = {
+                "t": d(t, (N,), torch.int32), "T0": d(T0, (N,)), "Tw0": d(Tw0, (N,)),
+                "E0": d(np.nan_to_num(np.asarray(E0, dtype=float)), (N,)),
+                "counter": d(counter, (N,), torch.int32), "winter": d(winter, (N,), torch.int32),
+                "draw": d(draw, (H + 1, N)), "oat": d(oat, (H + 1, N)), "ghi": d(ghi, (H + 1, N)),
+                "price": d(price, (H, N)),
+            }
+            ex = L.Explicit(**{k: L.ptr(v) for k, v in ex_t.items()})
+            self._call(self.lib.dragg_mpc_solve_explicit, self._problem(), ex, self._hash(), self._out(), stream=stream)
+            self._keep = ex_t
+            return self.status
 
     def aggregate(self, stream=None):
         """collect_data sums (aggregator.py:751-753) -> device tensor [agg_load, forecast_load, agg_cost].
         A home whose fields are absent (a crashed home: the reference raises KeyError in
         collect_data, aggregator.py:750-752) makes the sums NaN."""
         with torch.cuda.device(self.device):
-            return self._aggregate(stream)
-
-    def _aggregate(self, stream):
-        self.drain(stream)
-        hsh = self._hash()
-        L.check(self.lib.dragg_mpc_aggregate(ctypes.byref(self.dims), ctypes.byref(hsh), L.ptr(self.agg),
-                                             L.stream_ptr(stream, self.device)))
-        return self.agg
+            self.drain(stream)
+            self._call(self.lib.dragg_mpc_aggregate, self._hash(), L.ptr(self.agg), stream=stream)
+            return self.agg
 
     # ------------------------------------------------------------------ grouped batches
     def replicate_from(self, base, stream=None):
@@ -422,9 +403,7 @@ class MPCBatch:
                              f"take a batch of {base.N} homes (H = {base.H})")
         with torch.cuda.device(self.device):
             base.drain(stream)
-            src, dst = base._hash(), self._hash()
-            L.check(self.lib.dragg_mpc_replicate(ctypes.byref(self.dims), ctypes.byref(src), ctypes.byref(dst),
-                                                 L.stream_ptr(stream, self.device)))
+            self._call(self.lib.dragg_mpc_replicate, base._hash(), self._hash(), stream=stream)
 
     def aggregate_groups(self, stream=None):
         """collect_data's sums of every group -> device tensor [G][3]; row g is bit-identical to
@@ -432,21 +411,16 @@ class MPCBatch:
         with torch.cuda.device(self.device):
             if getattr(self, "agg_groups", None) is None:
                 self.agg_groups = torch.zeros((self.groups, 3), dtype=torch.float64, device=self.device)
-            hsh = self._hash()
-            L.check(self.lib.dragg_mpc_aggregate_groups(ctypes.byref(self.dims), ctypes.byref(hsh),
-                                                        L.ptr(self.agg_groups), L.stream_ptr(stream, self.device)))
+            self._call(self.lib.dragg_mpc_aggregate_groups, self._hash(), L.ptr(self.agg_groups), stream=stream)
             return self.agg_groups
 
     def season_noise(self, t, stream=None):
         with torch.cuda.device(self.device):
-            return self._season_noise(t, stream)
+            out = torch.empty((self.H, self.N), dtype=torch.float64, device=self.device)
+            self._call(self.lib.dragg_mpc_season_noise, self.seed, self.home_offset, self.home_stride, int(t),
+                       L.ptr(out), stream=stream)
+            return out
 
-    def _season_noise(self, t, stream):
-        out = torch.empty((self.H, self.N), dtype=torch.float64, device=self.device)
-        L.check(self.lib.dragg_mpc_season_noise(ctypes.byref(self.dims), self.seed, self.home_offset,
-                                                self.home_stride, int(t), L.ptr(out),
-                                                L.stream_ptr(stream, self.device)))
-        return out
 
     # ------------------------------------------------------------------ hash views
     def hash_dict(self, i, as_str=True):

@@ -248,6 +248,60 @@ def test_side_grid_clamped_to_scratch_slots(lib_path, monkeypatch):
         L.reload_knobs()
 
 
+def test_entry_points_refuse_bad_arguments(lib_path):
+    """The refusal table of the solve entry points: every call below is refused (or is a zero-home
+    no-op) before any HIP call, so it runs without a GPU on dummy pointers.  One thing is knocked out
+    of a valid call per case.  (Only refused calls and no-ops: a call the library accepts would launch
+    kernels on these addresses.)"""
+    from dragg_amd import _lib as L
+    lib = L.load()
+    E_ARG, E_HORIZON, DUMMY = -1, -4, 0x1000
+
+    def ptrs(cls):
+        return {f: DUMMY for f, ty in cls._fields_ if ty is L.c_dp}
+
+    def call(entry, dims={}, prob={}, hsh={}, out={}, ex={}, lag={}, t=0):
+        d = L.Dims(**{**dict(n_homes=4, horizon=24, sub_steps=6, dt=4, n_draw_hours=48, n_env=200, n_rp=1,
+                             int_mode=L.INT_ROUND), **dims})
+        p, h, o = L.Problem(**{**ptrs(L.Problem), **prob}), L.Hash(**{**ptrs(L.Hash), **hsh}), L.Out(**{**ptrs(L.Out), **out})
+        e, lg = L.Explicit(**{**ptrs(L.Explicit), **ex}), L.Lag(**{**ptrs(L.Lag), **lag})
+        r = ctypes.byref
+        if entry == "step":
+            return lib.dragg_mpc_step(r(d), r(p), r(h), r(o), t, None, None)
+        if entry in ("step_main", "step_side"):
+            return getattr(lib, "dragg_mpc_" + entry)(r(d), r(p), r(h), r(o), t, r(lg), None)
+        if entry == "solve_explicit":
+            return lib.dragg_mpc_solve_explicit(r(d), r(p), r(e), r(h), r(o), None)
+        assert entry == "lag_reset"
+        return lib.dragg_mpc_lag_reset(r(d), r(lg), t, None)
+
+    table = []          # (entry, what is knocked out, expected code)
+    for f in ("params", "home_type", "draw_hourly", "oat", "ghi", "tou", "reward_price", "workspace"):
+        table.append(("step", dict(prob={f: None}), E_ARG))
+    for f in ("vals", "fc"):
+        table.append(("step", dict(hsh={f: None}), E_ARG))
+    for f in ("status", "iters", "obj", "relax_obj"):
+        table.append(("step", dict(out={f: None}), E_ARG))
+    table += [("step", dict(t=-1), E_ARG), ("step", dict(dims=dict(n_rp=5)), E_ARG),
+              ("step", dict(dims=dict(n_env=24)), E_ARG), ("step", dict(dims=dict(sub_steps=16)), E_ARG),
+              ("step", dict(dims=dict(horizon=160)), E_HORIZON), ("step", dict(dims=dict(n_homes=0)), 0)]
+    for entry in ("step_main", "step_side"):
+        for f in ("clock", "skipped", "narrow"):
+            table.append((entry, dict(lag={f: None}), E_ARG))
+        table += [(entry, dict(dims=dict(n_groups=2)), E_ARG), (entry, dict(dims=dict(int_mode=L.INT_RELAX)), E_ARG),
+                  (entry, dict(t=2 ** 30 - 1), E_ARG), (entry, dict(prob=dict(workspace=None)), E_ARG),
+                  (entry, dict(dims=dict(n_homes=0)), 0)]
+    table.append(("step_side", dict(lag=dict(side_workspace=None)), E_ARG))
+    for f, _ in L.Explicit._fields_:
+        table.append(("solve_explicit", dict(ex={f: None}), E_ARG))
+    table += [("solve_explicit", dict(dims=dict(n_groups=2)), E_ARG), ("solve_explicit", dict(dims=dict(n_homes=0)), 0)]
+    table += [("lag_reset", dict(lag=dict(clock=None)), E_ARG), ("lag_reset", dict(dims=dict(n_groups=2)), E_ARG),
+              ("lag_reset", dict(t=2 ** 30 - 1), E_ARG)]
+    assert len(table) == 20 + 2 * 8 + 1 + 12 + 3
+    got = [(entry, knock, call(entry, **knock)) for entry, knock, _ in table]
+    assert got == table
+
+
 def test_stale_library_refused(tmp_path, monkeypatch, lib_path):
     """The library carries its sources' sha-256 (dragg_amd/build.py); the loader refuses one whose stamp
     is not the sources' beside it."""
