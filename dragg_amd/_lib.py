@@ -89,6 +89,32 @@ def lag_list_ints(n):
     return n + 4
 
 
+def workspace_regions(N, H, cells=False):
+    """Byte offset of every region of the round-mode workspace, in order, and the total (mirrors
+    mpc_kernel.hip's par_region_bytes ... direct_workspace_bytes; dragg_mpc_workspace_bytes is the total,
+    dragg_mpc_side_workspace_bytes the span [deferred, w_rows)).  A list is [N] i32 entries, then its
+    length and take counter.  cells: with a reward-price list (dims.n_rp > 1)."""
+    def up(x):
+        return (x + 255) // 256 * 256
+    # mpc_kernel.hip's NB_CAP, NF_BIG, NF_MID, SECOND_SLOTS, MID_SLOTS_MAX, NARROW_SLOTS, NCELL (= CELL_STRIDE)
+    NB_CAP, NF_BIG, NF_MID, SECOND_SLOTS, MID_SLOTS, NARROW_SLOTS, NCELL = 336, 2048, 384, 512, 2048, 16, 1024
+    # step_slot_bytes(): [2][POOL_CAP = 2^20] f64, [2][MC_CAP = 8 NP_CAP = 8 x 32768] i32, [2][LW_ROWS = 256][64] (x, v)
+    step_slot = 2 * 2 ** 20 * 8 + 2 * 8 * 32768 * 4 + 2 * 256 * 64 * 16
+    list_bytes = (N + 2) * 4
+    r = {"back_pointers": 0}                           # [N][H][NB_CAP] u16
+    r["solutions"] = up(N * H * NB_CAP * 2)            # [N][8H] f64 stage-slot solutions
+    r["deferred"] = r["solutions"] + N * 8 * H * 8     # list: hot -> mid (not 256-aligned)
+    r["big_rows"] = up(r["deferred"] + list_bytes)     # [SECOND_SLOTS][H][NF_BIG] u16
+    r["steps_list"] = up(r["big_rows"] + SECOND_SLOTS * H * NF_BIG * 2)    # list: any -> step-function DP
+    r["steps_pools"] = up(r["steps_list"] + list_bytes)                    # [min(N, 16)] block slots
+    r["mid_list"] = up(r["steps_pools"] + min(N, NARROW_SLOTS) * step_slot)   # list: mid -> big
+    r["mid_rows"] = up(r["mid_list"] + list_bytes)     # [MID_SLOTS][H][NF_MID] u16
+    r["w_rows"] = up(r["mid_rows"] + MID_SLOTS * H * NF_MID * 2)           # [N][H + 1][64] (x, v)
+    r["cell_rows"] = up(r["w_rows"] + N * (H + 1) * 64 * 16)               # [N][H + 1][NCELL] u16 (cells)
+    r["total"] = r["cell_rows"] + (N * (H + 1) * NCELL * 2 if cells else 0)
+    return r
+
+
 NLAUNCH = 4                    # DRAGG_NLAUNCH: hot, big, mid, narrow (dragg_mpc_kernel_info)
 LAUNCH_NAMES = ["hot", "big", "mid", "narrow"]
 

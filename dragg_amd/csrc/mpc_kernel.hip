@@ -19,6 +19,7 @@
 #include <limits.h>
 #include <stdlib.h>
 #include <stdio.h>
+#include <type_traits>
 
 #include "../../include/dragg_mi355x.h"
 
@@ -93,6 +94,20 @@ __host__ __device__ constexpr int xch_passes(int cap) { return (cap * 7 + 63) / 
 __host__ __device__ constexpr int xch_bytes(int cap) { return xch_passes(cap) * 8 + 8 * 8 + 8 * 5 * 4; }
 constexpr int NW_MID = 1;                // waves per home of the mid launch
 constexpr int NW_BIG = 4;                // waves per home of the big launch (2 blocks per CU: 8 waves)
+// A front DP's capacities, named once per launch: its LDS layout reserves them and dp_front_as runs
+// dp_front with them.  CAP / CAPB: labels of a front without / with the W table behind it, PS: stride of
+// the back-pointer rows, NBK: key / cost buckets per stage.
+struct HotDP { static constexpr int CAP = NF_HOT, CAPB = NF_HOT, PS = NB_CAP, NBK = NTB_HOT; };
+// the second launches' regular front DP, in the direct layout's lab / rmin (64 key / cost buckets, as in
+// the hot launch: the RL tank chain's DP here, rotated A/B round 6: RL action -2.0 % against 192
+// buckets, 128: -0.6 %; the full day unchanged; the layout keeps NTB bucket records)
+struct RegDP { static constexpr int CAP = NF, CAPB = NF_BOUND, PS = NB_CAP, NBK = NTB_HOT; };
+struct MidDP { static constexpr int CAP = NF_MID, CAPB = NF_MID, PS = NF_MID, NBK = NTB_MID; };
+struct BigDP { static constexpr int CAP = NF_BIG, CAPB = NF_BIG, PS = NF_BIG, NBK = NTB_BIG; };
+static_assert(RegDP::NBK <= NTB, "the direct layout keeps NTB bucket records");
+// the dynamic LDS limit the launches raise: the 160 KB of a CU less room for the kernels' static
+// LDS (the persistent launches' take slot)
+constexpr int LDS_DYN_MAX = 160 * 1024 - 256;
 enum Slot { S_U = 0, S_W = 1, S_T = 2, S_TW = 3, S_CH = 4, S_DIS = 5, S_E = 6, S_PAD = 7 };
 
 constexpr double SIGMA = 1e-6;
@@ -1514,7 +1529,7 @@ struct LdsD {
 __host__ __device__ inline int seg_cap(int H) { return ((2 * H + 2 + 63) / 64) * 64; }
 
 // The battery LP runs after the thermal DPs: its segment lists live in lab (sgS) and rmin
-// (sgL); for H up to ~60 its recovery arrays (bx0, bp1, bp2) also fit in lab and the
+// (sgL); for H up to 95 its recovery arrays (bx0, bp1, bp2) also fit in lab and the
 // objective's p_grid (t2) in rmin ("compact" layout), else they get arrays of their own.
 __host__ __device__ inline bool direct_compact(int H) {
     return 2 * seg_cap(H) + 3 * H <= 2 * NB_CAP && 2 * seg_cap(H) + H <= 2 * (NB_CAP + 8);
@@ -1581,6 +1596,17 @@ __host__ __device__ inline size_t direct_workspace_bytes(int N, int H, bool cell
     return cell_region_offset(N, H) + cell_region_bytes(N, H, cells);
 }
 
+// byte offsets into a block's dynamic LDS come from one allocator (host launch sizes and device carves alike)
+struct LdsAlloc {
+    int p;
+    __host__ __device__ int take(int bytes, int align) {
+        p = (p + align - 1) / align * align;
+        const int r = p;
+        p += bytes;
+        return r;
+    }
+};
+
 struct DirectLayout {
     int draw, oat, ghi, price, cA, cC, cq, sc, t2, bx0, bp1, bp2, lab, rmin, tail;
     int kb, cb, mh, kl, flo, fhi;             // dp_front tail
@@ -1595,78 +1621,76 @@ struct DirectLayout {
 // other way: 7 homes per CU cost +11 % time, 6 +43 %).
 __host__ __device__ inline DirectLayout front_layout(int H) {
     DirectLayout o{};
-    int p = 0;
-    auto take = [&](int bytes, int align) { p = (p + align - 1) / align * align; const int r = p; p += bytes; return r; };
-    o.draw = take(8 * (H + 1), 16);
-    o.oat = take(8 * (H + 1), 8);
-    o.ghi = take(8 * (H + 1), 8);
-    o.price = take(8 * (H + 1), 8);
-    o.cA = take(8 * H, 8);
-    o.cC = take(8 * H, 8);
-    o.cq = take(8 * H, 8);
-    o.sc = take(8 * 32, 8);
-    o.tail = p;
-    o.lab = take(16 * NF_HOT, 16);
-    o.rmin = take(16 * NF_HOT, 16);
-    o.wl = take(8 * 3 * WAVE, 16);
-    o.kb = take(16 * NTB_HOT, 16);                  // per bucket {key ref u64, mh u32, pad}: one 16-B load
-    o.cb = take(16 * NTB_HOT, 16);                  // per bucket {cost ref u64, kl u32, pad}
+    LdsAlloc a{0};
+    o.draw = a.take(8 * (H + 1), 16);
+    o.oat = a.take(8 * (H + 1), 8);
+    o.ghi = a.take(8 * (H + 1), 8);
+    o.price = a.take(8 * (H + 1), 8);
+    o.cA = a.take(8 * H, 8);
+    o.cC = a.take(8 * H, 8);
+    o.cq = a.take(8 * H, 8);
+    o.sc = a.take(8 * 32, 8);
+    o.tail = a.p;
+    o.lab = a.take(16 * HotDP::CAP, 16);
+    o.rmin = a.take(16 * HotDP::CAP, 16);
+    o.wl = a.take(8 * 3 * WAVE, 16);
+    o.kb = a.take(16 * HotDP::NBK, 16);             // per bucket {key ref u64, mh u32, pad}: one 16-B load
+    o.cb = a.take(16 * HotDP::NBK, 16);             // per bucket {cost ref u64, kl u32, pad}
     o.mh = o.kb + 8;
     o.kl = o.cb + 8;
-    o.flo = take(4 * (H + 1), 4);
-    o.fhi = take(4 * (H + 1), 4);
-    o.xch = take(xch_bytes(NF_HOT), 16);
-    const int dp_end = p;
-    p = o.tail;                                  // the battery LP's arrays over the dead DP region
-    o.sgS = take(16 * seg_cap(H), 16);
-    o.sgL = take(16 * seg_cap(H), 16);
-    o.bx0 = take(8 * H, 8);
-    o.bp1 = take(8 * H, 8);
-    o.bp2 = take(8 * H, 8);
-    o.t2 = take(8 * H, 8);
+    o.flo = a.take(4 * (H + 1), 4);
+    o.fhi = a.take(4 * (H + 1), 4);
+    o.xch = a.take(xch_bytes(HotDP::CAP), 16);
+    const int dp_end = a.p;
+    a.p = o.tail;                                // the battery LP's arrays over the dead DP region
+    o.sgS = a.take(16 * seg_cap(H), 16);
+    o.sgL = a.take(16 * seg_cap(H), 16);
+    o.bx0 = a.take(8 * H, 8);
+    o.bp1 = a.take(8 * H, 8);
+    o.bp2 = a.take(8 * H, 8);
+    o.t2 = a.take(8 * H, 8);
     o.cand = o.rt = o.candp = o.tarr = o.rsrc = -1;
-    o.bytes = (max(dp_end, p) + 15) / 16 * 16;
+    o.bytes = (max(dp_end, a.p) + 15) / 16 * 16;
     return o;
 }
 
 __host__ __device__ inline DirectLayout direct_layout(int H, int S) {
     DirectLayout o{};
-    int p = 0;
-    auto take = [&](int bytes, int align) { p = (p + align - 1) / align * align; const int r = p; p += bytes; return r; };
-    o.draw = take(8 * (H + 1), 16);
-    o.oat = take(8 * (H + 1), 8);
-    o.ghi = take(8 * (H + 1), 8);
-    o.price = take(8 * (H + 1), 8);
-    o.cA = take(8 * H, 8);
-    o.cC = take(8 * H, 8);
-    o.cq = take(8 * H, 8);
-    o.sc = take(8 * 32, 8);
+    LdsAlloc a{0};
+    o.draw = a.take(8 * (H + 1), 16);
+    o.oat = a.take(8 * (H + 1), 8);
+    o.ghi = a.take(8 * (H + 1), 8);
+    o.price = a.take(8 * (H + 1), 8);
+    o.cA = a.take(8 * H, 8);
+    o.cC = a.take(8 * H, 8);
+    o.cq = a.take(8 * H, 8);
+    o.sc = a.take(8 * 32, 8);
     o.t2 = o.bx0 = o.bp1 = o.bp2 = -1;
     if (!direct_compact(H)) {
-        o.t2 = take(8 * H, 8);
-        o.bx0 = take(8 * H, 8);
-        o.bp1 = take(8 * H, 8);
-        o.bp2 = take(8 * H, 8);
+        o.t2 = a.take(8 * H, 8);
+        o.bx0 = a.take(8 * H, 8);
+        o.bp1 = a.take(8 * H, 8);
+        o.bp2 = a.take(8 * H, 8);
     }
-    o.lab = take(16 * NB_CAP, 16);
-    o.rmin = take(16 * (NB_CAP + 8), 16);
-    o.tail = p;
+    o.lab = a.take(16 * NB_CAP, 16);
+    o.rmin = a.take(16 * (NB_CAP + 8), 16);
+    o.tail = a.p;
     // dp_front tail
-    o.kb = take(16 * NTB, 16);                  // per bucket {key ref u64, mh u32, pad}: one 16-B load
-    o.cb = take(16 * NTB, 16);                  // per bucket {cost ref u64, kl u32, pad}
+    o.kb = a.take(16 * NTB, 16);                // per bucket {key ref u64, mh u32, pad}: one 16-B load
+    o.cb = a.take(16 * NTB, 16);                // per bucket {cost ref u64, kl u32, pad}
     o.mh = o.kb + 8;
     o.kl = o.cb + 8;
-    o.flo = take(4 * (H + 1), 4);
-    o.fhi = take(4 * (H + 1), 4);
-    const int end_front = p;
+    o.flo = a.take(4 * (H + 1), 4);
+    o.fhi = a.take(4 * (H + 1), 4);
+    const int end_front = a.p;
     // dp_zspace tail (same origin)
-    p = o.tail;
-    o.cand = take(16 * NBND * (S + 1), 16);
-    o.rt = take(8 * (H + 2), 8);
-    o.candp = take(4 * NBND * (S + 1), 4);
-    o.tarr = take(2 * NB_CAP, 2);
-    o.rsrc = take(2 * (NB_CAP + 8), 2);
-    o.bytes = (max(end_front, p) + 15) / 16 * 16;
+    a.p = o.tail;
+    o.cand = a.take(16 * NBND * (S + 1), 16);
+    o.rt = a.take(8 * (H + 2), 8);
+    o.candp = a.take(4 * NBND * (S + 1), 4);
+    o.tarr = a.take(2 * NB_CAP, 2);
+    o.rsrc = a.take(2 * (NB_CAP + 8), 2);
+    o.bytes = (max(end_front, a.p) + 15) / 16 * 16;
     return o;
 }
 
@@ -1679,104 +1703,85 @@ __host__ __device__ inline int direct_lds_bytes(int H, int S) { return direct_la
 struct NarrowLayout { int off, cnt, wc, lc, red, xr, rng, rl, rh, dlo, dhi, xv, lt, sp, spb, bytes; };
 __host__ __device__ inline NarrowLayout narrow_layout(int H, int S, int lds_cap = 0) {
     NarrowLayout o{};
-    int p = direct_layout(H, S).bytes;
-    auto take = [&](int bytes, int align) { p = (p + align - 1) / align * align; const int r = p; p += bytes; return r; };
-    o.off = take(4 * (H + 1), 4);
-    o.cnt = take(4 * (H + 1), 4);
-    o.wc = take(4 * (H + 1), 4);
-    o.lc = take(4 * (H + 1), 4);
-    o.red = take(4 * 32, 4);
-    o.xr = take(4 * (NT_STEPS / 64) * STEP_MAXU, 4);
-    o.rng = take(4 * (4 * STEP_MAXU + 8), 4);
-    o.rl = take(8 * (H + 1), 8);
-    o.rh = take(8 * (H + 1), 8);
-    o.dlo = take(8 * (H + 1), 8);
-    o.dhi = take(8 * (H + 1), 8);
-    o.xv = take(8 * STEP_MAXU, 8);
-    o.lt = take(8 * (3 * WAVE + 2), 16);
+    LdsAlloc a{direct_layout(H, S).bytes};
+    o.off = a.take(4 * (H + 1), 4);
+    o.cnt = a.take(4 * (H + 1), 4);
+    o.wc = a.take(4 * (H + 1), 4);
+    o.lc = a.take(4 * (H + 1), 4);
+    o.red = a.take(4 * 32, 4);
+    o.xr = a.take(4 * (NT_STEPS / 64) * STEP_MAXU, 4);
+    o.rng = a.take(4 * (4 * STEP_MAXU + 8), 4);
+    o.rl = a.take(8 * (H + 1), 8);
+    o.rh = a.take(8 * (H + 1), 8);
+    o.dlo = a.take(8 * (H + 1), 8);
+    o.dhi = a.take(8 * (H + 1), 8);
+    o.xv = a.take(8 * STEP_MAXU, 8);
+    o.lt = a.take(8 * (3 * WAVE + 2), 16);
     // the pool takes what is left of the CU's LDS (>= the waves' PL tables of lp_cut)
-    o.sp = take(0, 16);
+    o.sp = a.take(0, 16);
     // (lds_cap > 0, DRAGG_NARROW_LDS_KB: a smaller block that shares a CU with hot-launch blocks -- it need
     // not wait for a CU to drain completely -- at the price of stages that spill to the workspace sooner)
-    const int cap_ = lds_cap > 0 ? min(lds_cap, 160 * 1024 - 256) : 160 * 1024 - 256;
+    const int cap_ = lds_cap > 0 ? min(lds_cap, LDS_DYN_MAX) : LDS_DYN_MAX;
     o.spb = max(NT_STEPS / 64 * 6 * WAVE * 8, (cap_ - o.sp - 64) / 64 * 64);
-    p = o.sp + o.spb;
-    o.bytes = (p + 15) / 16 * 16;
+    o.bytes = (o.sp + o.spb + 15) / 16 * 16;
     return o;
 }
 
-// The second launch: the direct layout, and over its DP arrays (from lab on; the bucketed DP
-// is done with them, its schedule is in the global solution array) the big exact pass's
-// fronts [NF_BIG], W table, bucket arrays and hull.
+// The second launches (C = MidDP, BigDP): the direct layout, and over its DP arrays (from lab on; the
+// bucketed DP is done with them, its schedule is in the global solution array) the exact pass's
+// fronts [C::CAP], W table, bucket arrays and hull.  Mid: ~20 KB at H = 48, ~7 blocks per CU; big: 2.
+// (the RL path's cell rows are read from the workspace, not staged in LDS: 4 KB per block more cost a
+// block per CU -- measured RL action 18.0 ms against 20.1 ms with the row in LDS)
 struct BigLayout {
     int fa, fb, wl, kb, cb, mh, kl, flo, fhi, xch, bytes;
 };
-__host__ __device__ inline BigLayout big_layout(int H, int S) {
+template <class C>
+__host__ __device__ inline BigLayout second_layout(int H, int S) {
     const DirectLayout d = direct_layout(H, S);
     BigLayout o{};
-    int p = d.lab;
-    auto take = [&](int bytes, int align) { p = (p + align - 1) / align * align; const int r = p; p += bytes; return r; };
-    o.fa = take(16 * NF_BIG, 16);
-    o.fb = take(16 * NF_BIG, 16);
-    o.wl = take(8 * 3 * WAVE, 16);
-    o.kb = take(16 * NTB_BIG, 16);                  // per bucket {key ref u64, mh u32, pad}: one 16-B load
-    o.cb = take(16 * NTB_BIG, 16);                  // per bucket {cost ref u64, kl u32, pad}
+    LdsAlloc a{d.lab};
+    o.fa = a.take(16 * C::CAP, 16);
+    o.fb = a.take(16 * C::CAP, 16);
+    o.wl = a.take(8 * 3 * WAVE, 16);
+    o.kb = a.take(16 * C::NBK, 16);                 // per bucket {key ref u64, mh u32, pad}: one 16-B load
+    o.cb = a.take(16 * C::NBK, 16);                 // per bucket {cost ref u64, kl u32, pad}
     o.mh = o.kb + 8;
     o.kl = o.cb + 8;
-    o.flo = take(4 * (H + 1), 4);
-    o.fhi = take(4 * (H + 1), 4);
-    p = max(p, d.bytes);                         // past the direct layout too: the regular front DP of
-    o.xch = take(max(xch_bytes(NF_BIG), xch_bytes(NF)), 16);   // the (multi-wave) launch uses it as well
-    o.bytes = (p + 15) / 16 * 16;
+    o.flo = a.take(4 * (H + 1), 4);
+    o.fhi = a.take(4 * (H + 1), 4);
+    a.p = max(a.p, d.bytes);                     // past the direct layout too: the regular front DP of
+    o.xch = a.take(max(xch_bytes(C::CAP), xch_bytes(RegDP::CAP)), 16);   // the (multi-wave) launch uses it as well
+    o.bytes = (a.p + 15) / 16 * 16;
     return o;
 }
 
-// The mid launch: the direct layout, and over its DP arrays the exact pass's fronts [NF_MID],
-// W table, bucket arrays and hull: ~20 KB at H = 48, ~7 blocks per CU (the big layout: 2)
-__host__ __device__ inline BigLayout mid_layout(int H, int S) {
-    const DirectLayout d = direct_layout(H, S);
-    BigLayout o{};
-    int p = d.lab;
-    auto take = [&](int bytes, int align) { p = (p + align - 1) / align * align; const int r = p; p += bytes; return r; };
-    o.fa = take(16 * NF_MID, 16);
-    o.fb = take(16 * NF_MID, 16);
-    o.wl = take(8 * 3 * WAVE, 16);
-    o.kb = take(16 * NTB_MID, 16);                  // per bucket {key ref u64, mh u32, pad}: one 16-B load
-    o.cb = take(16 * NTB_MID, 16);                  // per bucket {cost ref u64, kl u32, pad}
-    o.mh = o.kb + 8;
-    o.kl = o.cb + 8;
-    o.flo = take(4 * (H + 1), 4);
-    o.fhi = take(4 * (H + 1), 4);
-    p = max(p, d.bytes);
-    o.xch = take(max(xch_bytes(NF_MID), xch_bytes(NF)), 16);
-    // (the RL path's cell rows are read from the workspace, not staged in LDS: 4 KB per block more cost a
-    // block per CU -- measured RL action 18.0 ms against 20.1 ms with the row in LDS)
-    o.bytes = (p + 15) / 16 * 16;
-    return o;
-}
-
-DEV LdsD carve_front(double* smem, int H) {
-    const DirectLayout o = front_layout(H);
-    char* b = reinterpret_cast<char*>(smem);
+// the pointers both carves share: the head, lab and rmin, dp_front's bucket arrays and hulls
+DEV LdsD carve_common(char* b, const DirectLayout& o) {
     auto D = [&](int off) { return reinterpret_cast<double*>(b + off); };
-    LdsD L{};
+    LdsD L{};                                                    // (x, par: global workspace, set by the kernel)
     L.draw = D(o.draw); L.oat = D(o.oat); L.ghi = D(o.ghi); L.price = D(o.price);
-    L.x = nullptr;                                               // global workspace (kernel)
     L.cA = D(o.cA); L.cC = D(o.cC); L.cq = D(o.cq);
     L.sc = D(o.sc);
     L.lab = reinterpret_cast<double2*>(b + o.lab);
     L.rmin = reinterpret_cast<double2*>(b + o.rmin);
-    L.wl = D(o.wl);
     L.kb = reinterpret_cast<unsigned long long*>(b + o.kb);
     L.cb = reinterpret_cast<unsigned long long*>(b + o.cb);
     L.mh = reinterpret_cast<unsigned*>(b + o.mh);
     L.kl = reinterpret_cast<unsigned*>(b + o.kl);
     L.flo = reinterpret_cast<unsigned*>(b + o.flo);
     L.fhi = reinterpret_cast<unsigned*>(b + o.fhi);
+    return L;
+}
+
+DEV LdsD carve_front(double* smem, int H) {
+    const DirectLayout o = front_layout(H);
+    char* b = reinterpret_cast<char*>(smem);
+    auto D = [&](int off) { return reinterpret_cast<double*>(b + off); };
+    LdsD L = carve_common(b, o);
+    L.wl = D(o.wl);
     L.sgS = D(o.sgS); L.sgL = D(o.sgL);
     L.bx0 = D(o.bx0); L.bp1 = D(o.bp1); L.bp2 = D(o.bp2); L.t2 = D(o.t2);
     L.xch = b + o.xch;
-    L.par = nullptr;                                             // set by the kernel
     return L;
 }
 
@@ -1784,19 +1789,7 @@ DEV LdsD carve_direct(double* smem, int H, int S) {
     const DirectLayout o = direct_layout(H, S);
     char* b = reinterpret_cast<char*>(smem);
     auto D = [&](int off) { return reinterpret_cast<double*>(b + off); };
-    LdsD L;
-    L.draw = D(o.draw); L.oat = D(o.oat); L.ghi = D(o.ghi); L.price = D(o.price);
-    L.x = nullptr;                                               // global workspace (kernel)
-    L.cA = D(o.cA); L.cC = D(o.cC); L.cq = D(o.cq);
-    L.sc = D(o.sc);
-    L.lab = reinterpret_cast<double2*>(b + o.lab);
-    L.rmin = reinterpret_cast<double2*>(b + o.rmin);
-    L.kb = reinterpret_cast<unsigned long long*>(b + o.kb);
-    L.cb = reinterpret_cast<unsigned long long*>(b + o.cb);
-    L.mh = reinterpret_cast<unsigned*>(b + o.mh);
-    L.kl = reinterpret_cast<unsigned*>(b + o.kl);
-    L.flo = reinterpret_cast<unsigned*>(b + o.flo);
-    L.fhi = reinterpret_cast<unsigned*>(b + o.fhi);
+    LdsD L = carve_common(b, o);
     L.cand = reinterpret_cast<double2*>(b + o.cand);
     L.rt = D(o.rt);
     L.candp = reinterpret_cast<int*>(b + o.candp);
@@ -1814,7 +1807,6 @@ DEV LdsD carve_direct(double* smem, int H, int S) {
     } else {
         L.t2 = D(o.t2); L.bx0 = D(o.bx0); L.bp1 = D(o.bp1); L.bp2 = D(o.bp2);
     }
-    L.par = nullptr;                                             // set by the kernel
     return L;
 }
 
@@ -1827,6 +1819,32 @@ DEV Lds lp_view(const LdsD& D) {
     return L;
 }
 
+// Stage k's coefficients of the two thermal chains x_{k+1} = A x_k + g u_k + C, one function per chain for
+// every user (solve, presolve, round_lp's rounding, cell bound): the results depend on the expressions'
+// form, and the cell bound is a lower bound only of the chain the solve builds bit for bit.
+// indoor air (mpc_calc.py:314-317), from oat[k + 1]; A = h.aT at every stage
+DEV double air_C(const Home& h, double oat1) { return oat1 * h.iR * 3600 * h.inv_c; }
+// water heater (mpc_calc.py:330-332), from draw[k + 1]: A, and C less the indoor-air term h.e T_{k+1}
+DEV void tank_AC(const Home& h, double draw1, double& A, double& C) {
+    const double df = draw1 / h.V, rem = 1 - df, d15 = df * TAP;
+    A = rem + (-rem * h.iRw) * 3600 * h.inv_w;
+    C = d15 + ((-d15) * h.iRw) * 3600 * h.inv_w;
+}
+// prices that change at more than a quarter of the stages: RL reward prices (a tariff changes a few times
+// a day).  Every wave counts all stages.  The solve and the cell kernel must agree on the verdict.
+DEV bool rl_priced(const double* price, int H, int tid) {
+    int changes = 0;
+    for (int k = tid & (WAVE - 1); k < H; k += WAVE) changes += (k > 0 && price[k] != price[k - 1]) ? 1 : 0;
+    changes = dpp_isum(changes);
+    return changes * 4 > H;
+}
+// the cost of the schedule in slot sv of the solution rows (every wave sums all stages)
+DEV double sched_cost(const double* cq, const double* x, int sv, int H, int tid) {
+    double c = 0.0;
+    for (int k = tid & (WAVE - 1); k < H; k += WAVE) c += cq[k] * x[k * 8 + sv];
+    return dpp_sum(c);
+}
+
 // Exact interval feasibility of the T and E chains and the outer test of the Tw chain:
 // presolve_infeasible of the LP path, on the direct path's inputs.
 DEV bool presolve_direct(const Home& h, const LdsD& L, double twlo0, double twhi0, int lane) {
@@ -1834,15 +1852,13 @@ DEV bool presolve_direct(const Home& h, const LdsD& L, double twlo0, double twhi
     double Tlo = h.T0, Thi = h.T0, Wlo = h.Tw0, Whi = h.Tw0, Elo = h.E0, Ehi = h.E0;
     const double gS = h.g * h.S;
     // stage k's coefficients, one stage per lane (a division each, off the serial chain); the
-    // interval recursion then reads them with v_readlane (same expressions as the serial form)
+    // interval recursion then reads them with v_readlane
     const bool lanes = h.H <= WAVE;
     double bq = 0.0, cq = 0.0, dq = 0.0;
     const int wl = lane & (WAVE - 1);                 // every wave of the workgroup keeps a copy
     if (lanes && wl < h.H) {
-        bq = L.oat[wl + 1] * h.iR * 3600 * h.inv_c;
-        const double df = L.draw[wl + 1] / h.V, rem = 1 - df, d15 = df * TAP;
-        cq = rem + (-rem * h.iRw) * 3600 * h.inv_w;
-        dq = d15 + ((-d15) * h.iRw) * 3600 * h.inv_w;
+        bq = air_C(h, L.oat[wl + 1]);
+        tank_AC(h, L.draw[wl + 1], cq, dq);
     }
     const double edis = h.brate * (1.0 / h.etad) / h.dt, echg = h.brate * h.etac / h.dt;
     bool bad = false;
@@ -1851,10 +1867,8 @@ DEV bool presolve_direct(const Home& h, const LdsD& L, double twlo0, double twhi
         if (lanes) {
             bk = read_lane(bq, k); ck = read_lane(cq, k); dk = read_lane(dq, k);
         } else {
-            bk = L.oat[k + 1] * h.iR * 3600 * h.inv_c;
-            const double df = L.draw[k + 1] / h.V, rem = 1 - df, d15 = df * TAP;
-            ck = rem + (-rem * h.iRw) * 3600 * h.inv_w;
-            dk = d15 + ((-d15) * h.iRw) * 3600 * h.inv_w;
+            bk = air_C(h, L.oat[k + 1]);
+            tank_AC(h, L.draw[k + 1], ck, dk);
         }
         // no early exit: the flags are or-ed (the result is the same, and the recursion has no
         // branch waiting on each comparison)
@@ -2421,6 +2435,15 @@ struct FrontBufs {
     double c_lo, c_inv;                  // the grid: cell of x = floor((x - c_lo) c_inv)
     float c_off, c_sc;                   // the codes' offset and scale (cell_rows)
 };
+
+// dp_front with the capacities of configuration C (HotDP, RegDP, MidDP, BigDP), S = 6
+template <class C, int NW = 1, bool CELL = false, int ILP = 1>
+DEV int dp_front_as(const FrontBufs& B, int H, int tid, double g, double x0, double lo0, double hi0, double lo,
+                    double hi, int sx, int sv, bool use_bound = false, double ub_ext = INFINITY,
+                    double* best_out = nullptr, int beam_k = 0) {
+    return dp_front<6, C::CAP, C::CAPB, C::PS, C::NBK, NW, CELL, ILP>(B, H, tid, g, x0, lo0, hi0, lo, hi, sx, sv,
+                                                                      use_bound, ub_ext, best_out, beam_k);
+}
 
 // 1 / w to about 1 ulp: v_rcp_f64 and one Newton step (no IEEE division sequence)
 DEV double rcp_nr(double w) {
@@ -3470,7 +3493,7 @@ DEV bool round_duties(const Home& h, const Lds& L, int lane, uint16_t* par) {
     const bool front = h.S == 6 && par != nullptr && (f - L.Lf) <= 128 * H;
     for (int k = lane; k < H; k += WAVE) {
         cA[k] = h.aT;
-        cC[k] = L.oat[k + 1] * h.iR * 3600 * h.inv_c;
+        cC[k] = air_C(h, L.oat[k + 1]);
         cq[k] = L.q[k * 8 + S_U];
     }
     __syncthreads();
@@ -3482,9 +3505,10 @@ DEV bool round_duties(const Home& h, const Lds& L, int lane, uint16_t* par) {
         return false;
     }
     for (int k = lane; k < H; k += WAVE) {
-        const double df = L.draw[k + 1] / h.V, rem = 1 - df, d15 = df * TAP;
-        cA[k] = rem + (-rem * h.iRw) * 3600 * h.inv_w;
-        cC[k] = h.e * L.x[k * 8 + S_T] + (d15 + ((-d15) * h.iRw) * 3600 * h.inv_w);
+        double A, C;
+        tank_AC(h, L.draw[k + 1], A, C);
+        cA[k] = A;
+        cC[k] = h.e * L.x[k * 8 + S_T] + C;
         cq[k] = L.q[k * 8 + S_W];
     }
     __syncthreads();
@@ -3732,6 +3756,19 @@ struct StepBufs {
     int pool_cap;                 // breakpoints of all V_k of the chain (<= POOL_CAP; a knob shrinks it)
     long long work_cap;           // merge points over all stages of one pass: the work bound of a chain
 };
+
+// a StepBufs over the narrow layout nl of the LDS at `lds` and a block's step_slot_bytes() of workspace at `slot`
+DEV StepBufs step_bufs(void* lds, const NarrowLayout& nl, char* slot, int pool_cap, long long work_cap) {
+    char* const b = reinterpret_cast<char*>(lds);
+    auto I = [&](int off) { return reinterpret_cast<int*>(b + off); };
+    auto D = [&](int off) { return reinterpret_cast<double*>(b + off); };
+    double* const sw = reinterpret_cast<double*>(slot);
+    int* const swi = reinterpret_cast<int*>(sw + 2 * (size_t)POOL_CAP);
+    double2* const swr = reinterpret_cast<double2*>(swi + 2 * (size_t)MC_CAP);
+    return StepBufs{sw, sw + POOL_CAP, swi, swi + MC_CAP, swr, swr + (size_t)LW_ROWS * WAVE,
+                    I(nl.off), I(nl.cnt), I(nl.wc), I(nl.lc), I(nl.red), I(nl.xr), I(nl.rng),
+                    D(nl.rl), D(nl.rh), D(nl.dlo), D(nl.dhi), D(nl.xv), D(nl.lt), b + nl.sp, nl.spb, pool_cap, work_cap};
+}
 
 // exclusive prefix sums over the NT threads of the block of v[0..n) (n <= STEP_MAXU), in place
 // (xr: >= NT / 64 * STEP_MAXU ints of LDS, the caller's alone until a later barrier); one barrier
@@ -4329,6 +4366,7 @@ constexpr int BK_NEED = (int)(1u << 31);
 template <int PM, int MODE, int NW = 1, int ILP = 1>
 DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int first_chain, int eflags = 0) {
     constexpr bool SECOND = MODE == DM_BUCKET || MODE == DM_MID;   // the bucketed DP + an exact big-front pass
+    using XDP = std::conditional_t<MODE == DM_MID, MidDP, BigDP>;    // ... with these capacities
     constexpr int NT = NW * WAVE;
     const int lane = threadIdx.x;
     const int N = a.d.n_homes;
@@ -4385,15 +4423,11 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
         // chain 0: indoor air (mpc_calc.py:314-317), u = duty of the season's mode (:303-309);
         // chain 1: water heater given T (mpc_calc.py:330-332).  One DP instantiation for both.
         bool ok = true;
-        // prices that change at more than a quarter of the stages (RL reward prices; a tariff
-        // changes a few times a day) grow fronts past NF_BOUND at most homes (measured: 9,990 of
+        // RL prices grow fronts past NF_BOUND at most homes (measured: 9,990 of
         // 10,000): the hot launch hands these homes to the second one right away, which prunes
         // with the LP bound.  (Pruning by bound at every tariff boundary too: -14 % latency of
         // the slowest homes over the first 48 steps of the bench, but +13 % time over all 96.)
-        int changes = 0;                              // (every wave counts all stages)
-        for (int k = lane & (WAVE - 1); k < H; k += WAVE) changes += (k > 0 && D.price[k] != D.price[k - 1]) ? 1 : 0;
-        changes = dpp_isum(changes);
-        const bool rl_prices = changes * 4 > H;
+        const bool rl_prices = rl_priced(D.price, H, lane);
         const bool use_bound = rl_prices;
         if (MODE == DM_FRONT && a.force_steps) {
             if (lane == 0) nlist[atomicAdd(nlist + N, 1)] = home;
@@ -4412,7 +4446,7 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
                 const double wk = pow(h.gamma, (double)k) * D.price[k];
                 if (chain == 0) {
                     D.cA[k] = h.aT;
-                    D.cC[k] = D.oat[k + 1] * h.iR * 3600 * h.inv_c;
+                    D.cC[k] = air_C(h, D.oat[k + 1]);
                     D.cq[k] = wk * h.Pact;
 #if defined(DRAGG_FRONT_STATS) || defined(DRAGG_FRONT_STATS2) || defined(DRAGG_STAGE_PROF) || defined(DRAGG_STEP_PROF)
                     D.x[k * 8 + S_PAD] = 0.0;             // (the diagnostics' accumulators)
@@ -4421,9 +4455,10 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
                     // battery LP writes them all: the other homes skip the stores (1.5 KB per home-step)
                     if (h.batt) { D.x[k * 8 + S_CH] = 0.0; D.x[k * 8 + S_DIS] = 0.0; D.x[k * 8 + S_E] = 0.0; }
                 } else {
-                    const double df = D.draw[k + 1] / h.V, rem = 1 - df, d15 = df * TAP;
-                    D.cA[k] = rem + (-rem * h.iRw) * 3600 * h.inv_w;
-                    D.cC[k] = h.e * D.x[k * 8 + S_T] + (d15 + ((-d15) * h.iRw) * 3600 * h.inv_w);
+                    double A, C;
+                    tank_AC(h, D.draw[k + 1], A, C);
+                    D.cA[k] = A;
+                    D.cC[k] = h.e * D.x[k * 8 + S_T] + C;
                     D.cq[k] = wk * (h.S * h.Pw);
                 }
             }
@@ -4440,29 +4475,13 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
             if constexpr (MODE == DM_NARROW) {
                 // the exact step-function DP (any prices, any feasible sets)
                 const NarrowLayout nl = narrow_layout(H, a.d.sub_steps, a.narrow_lds);
-                char* const sb = reinterpret_cast<char*>(smem);
-                double* const sw = reinterpret_cast<double*>(lw + narrow_region_offset(N, H) +
-                                                             (size_t)slot * step_slot_bytes());
-                int* const swi = reinterpret_cast<int*>(sw + 2 * (size_t)POOL_CAP);
-                double2* const swr = reinterpret_cast<double2*>(swi + 2 * (size_t)MC_CAP);
-                const StepBufs SB{sw, sw + POOL_CAP, swi, swi + MC_CAP, swr, swr + (size_t)LW_ROWS * WAVE,
-                                  reinterpret_cast<int*>(sb + nl.off), reinterpret_cast<int*>(sb + nl.cnt),
-                                  reinterpret_cast<int*>(sb + nl.wc), reinterpret_cast<int*>(sb + nl.lc),
-                                  reinterpret_cast<int*>(sb + nl.red), reinterpret_cast<int*>(sb + nl.xr),
-                                  reinterpret_cast<int*>(sb + nl.rng),
-                                  reinterpret_cast<double*>(sb + nl.rl), reinterpret_cast<double*>(sb + nl.rh),
-                                  reinterpret_cast<double*>(sb + nl.dlo), reinterpret_cast<double*>(sb + nl.dhi),
-                                  reinterpret_cast<double*>(sb + nl.xv), reinterpret_cast<double*>(sb + nl.lt),
-                                  sb + nl.sp, nl.spb, min(POOL_CAP, max(64, a.step_pool_cap)),
-                                  a.step_work_cap > 0 ? a.step_work_cap : STEP_WORK_CAP};
+                const StepBufs SB = step_bufs(smem, nl, lw + narrow_region_offset(N, H) + (size_t)slot * step_slot_bytes(),
+                                              min(POOL_CAP, max(64, a.step_pool_cap)),
+                                              a.step_work_cap > 0 ? a.step_work_cap : STEP_WORK_CAP);
                 auto steps = [&](bool feas, bool cut, double U_ = INFINITY) {
                     return dp_steps<NT>(SB, D.cA, D.cC, D.cq, H, h.S, g, x0, lo0, hi0, lo, hi, D.x, sx, sv, lane, feas, cut, U_);
                 };
-                auto sched_cost = [&]() {                  // (every wave sums all stages)
-                    double c = 0.0;
-                    for (int k = lane & (WAVE - 1); k < H; k += WAVE) c += D.cq[k] * D.x[k * 8 + sv];
-                    return dpp_sum(c);
-                };
+                auto cost = [&]() { return sched_cost(D.cq, D.x, sv, H, lane); };
                 // an upper bound on the chain's optimum: the bucketed schedule the mid / big launch left in the
                 // solution rows; without one the feasibility pass (all duty costs 0: the feasible set as a few
                 // intervals, microseconds) decides whether any schedule exists and gives one
@@ -4473,7 +4492,7 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
                     const bool okb = dp_thermal<6>(h, D, lane, NT, g, x0, lo0, hi0, lo, hi, sx, sv);
                     eflags = BK_DONE | (okb ? BK_OK : 0);
                 }
-                double ub = (chain == first_chain && (eflags & BK_OK)) ? sched_cost() : INFINITY;
+                double ub = (chain == first_chain && (eflags & BK_OK)) ? cost() : INFINITY;
                 // the bucketed schedule (x, u per stage) kept aside in the chain's battery slots (zero until
                 // the battery LP, which runs after both chains): what stands in if the DP runs out of room
                 const bool have_bk = ub < INFINITY;
@@ -4496,7 +4515,7 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
                 r = ub < INFINITY ? 1 : steps(true, false);
                 PMARK(10);
                 if (r == 1) {
-                    if (!(ub < INFINITY)) ub = sched_cost();
+                    if (!(ub < INFINITY)) ub = cost();
                     double qabs = 0.0;
                     for (int k = lane & (WAVE - 1); k < H; k += WAVE) qabs += fabs(D.cq[k]) * h.S;
                     qabs = dpp_sum(qabs);
@@ -4517,7 +4536,7 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
                         if (U1 < U) {
                             lp_cut<NT>(SB, H, U1, lane);
                             PMARK(11);
-                            first = steps(false, true, U1) == 1 && sched_cost() <= U1;
+                            first = steps(false, true, U1) == 1 && cost() <= U1;
                             PMARK(12);
                             __syncthreads();
                         }
@@ -4579,17 +4598,13 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
                 // (a multi-wave second launch: the exchange area of its mid / big layout, past the
                 // direct layout's arrays)
                 char* const xch = MODE == DM_FRONT ? D.xch
-                                : reinterpret_cast<char*>(smem) + (MODE == DM_MID ? mid_layout(H, a.d.sub_steps).xch
-                                                                                  : big_layout(H, a.d.sub_steps).xch);
+                                                   : reinterpret_cast<char*>(smem) + second_layout<XDP>(H, a.d.sub_steps).xch;
                 const FrontBufs FB{D.lab, D.rmin, D.kb, D.cb, D.mh, D.kl, D.flo, D.fhi, D.cA, D.cC, D.cq, D.x, D.par,
                                    wg, wl, wl + WAVE, wl + 2 * WAVE, xch};
                 if constexpr (MODE == DM_FRONT)
-                    r = dp_front<6, NF_HOT, NF_HOT, NB_CAP, NTB_HOT, NW, false, ILP>(FB, H, lane, g, x0, lo0, hi0, lo, hi, sx, sv,
-                                                                                   use_bound);
+                    r = dp_front_as<HotDP, NW, false, ILP>(FB, H, lane, g, x0, lo0, hi0, lo, hi, sx, sv, use_bound);
                 else
-                    // (64 key / cost buckets, as in the hot launch: the RL tank chain's DP here, rotated A/B
-                    // round 6: RL action -2.0 % against 192 buckets, 128: -0.6 %; the full day unchanged)
-                    r = dp_front<6, NF, NF_BOUND, NB_CAP, NTB_HOT, NW>(FB, H, lane, g, x0, lo0, hi0, lo, hi, sx, sv, use_bound);
+                    r = dp_front_as<RegDP, NW>(FB, H, lane, g, x0, lo0, hi0, lo, hi, sx, sv, use_bound);
 #ifdef DRAGG_FRONT_STATS2
                 // diagnostic: the T chain's fronts when the bound is the optimum itself
                 if (c0 && r == 1 && use_bound) {
@@ -4616,7 +4631,7 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
                 return;
             } else {
                 pf.mark(DRAGG_PH_INTEGER);
-                const BigLayout bl = MODE == DM_MID ? mid_layout(H, a.d.sub_steps) : big_layout(H, a.d.sub_steps);
+                const BigLayout bl = second_layout<XDP>(H, a.d.sub_steps);
                 char* const sb = reinterpret_cast<char*>(smem);
                 double* const wl = reinterpret_cast<double*>(sb + bl.wl);
                 uint16_t* const bpar = MODE == DM_MID
@@ -4652,8 +4667,8 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
                     if constexpr (MODE == DM_MID) {
                         if (have_cells) {
                             __syncthreads();
-                            rb = dp_front<6, NF_MID, NF_MID, NF_MID, NTB_MID, NW, true>(FB, H, lane, g, x0, lo0, hi0, lo, hi, sx,
-                                                                                    sv, false, INFINITY, nullptr, BEAM_K);
+                            rb = dp_front_as<MidDP, NW, true>(FB, H, lane, g, x0, lo0, hi0, lo, hi, sx, sv, false, INFINITY,
+                                                              nullptr, BEAM_K);
                         }
                     }
                     ok = rb == 1;
@@ -4669,19 +4684,11 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
                 // dominance there: its fronts outgrow any capacity, measured)
                 if (h.S == 6 && r != -2) {
                     // the exact pass with big fronts, bounded by the schedule's cost
-                    double ub = INFINITY;
-                    if (ok) {                              // (every wave sums all stages)
-                        double c = 0.0;
-                        for (int k = lane & (WAVE - 1); k < H; k += WAVE) c += D.cq[k] * D.x[k * 8 + sv];
-                        ub = dpp_sum(c);
-                    }
+                    const double ub = ok ? sched_cost(D.cq, D.x, sv, H, lane) : INFINITY;
                     __syncthreads();
                     // keeps the schedule in D.x unless it finds (and writes) the optimum
                     auto cell_pass = [&](double U) {
-                        if constexpr (MODE == DM_MID)
-                            return dp_front<6, NF_MID, NF_MID, NF_MID, NTB_MID, NW, true>(FB, H, lane, g, x0, lo0, hi0, lo, hi, sx, sv, true, U);
-                        else
-                            return dp_front<6, NF_BIG, NF_BIG, NF_BIG, NTB_BIG, NW, true>(FB, H, lane, g, x0, lo0, hi0, lo, hi, sx, sv, true, U);
+                        return dp_front_as<XDP, NW, true>(FB, H, lane, g, x0, lo0, hi0, lo, hi, sx, sv, true, U);
                     };
                     if (have_cells) {
                         r2 = cell_pass(ub);
@@ -4714,10 +4721,8 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
                                 else if (r2 == -3) hi_u = U;              // still too many labels
                             }
                         }
-                    } else if constexpr (MODE == DM_MID) {
-                        r2 = dp_front<6, NF_MID, NF_MID, NF_MID, NTB_MID, NW>(FB, H, lane, g, x0, lo0, hi0, lo, hi, sx, sv, true, ub);
                     } else {
-                        r2 = dp_front<6, NF_BIG, NF_BIG, NF_BIG, NTB_BIG, NW>(FB, H, lane, g, x0, lo0, hi0, lo, hi, sx, sv, true, ub);
+                        r2 = dp_front_as<XDP, NW>(FB, H, lane, g, x0, lo0, hi0, lo, hi, sx, sv, true, ub);
                     }
                     pf.mark(DRAGG_PH_POLISH);             // (round: the mid / big exact pass)
                     if (MODE == DM_MID && r2 == -3) {         // past NF_MID: the big launch's 2,048-label fronts
@@ -4862,14 +4867,11 @@ __global__ __launch_bounds__(NT_CELL, 4) void cell_kernel(KArgs a) {
         __syncthreads();
         if (prologue<PM>(a, h, L, io, tid, NT_CELL, D.sc) == DRAGG_ST_ERR_MISSING) continue;
         derive(h);
-        int changes = 0;
-        for (int k = tid & (WAVE - 1); k < H; k += WAVE) changes += (k > 0 && D.price[k] != D.price[k - 1]) ? 1 : 0;
-        changes = dpp_isum(changes);
-        if (!(changes * 4 > H) || h.S != 6) continue;             // not RL-priced: the mid launch's regular path
+        if (!rl_priced(D.price, H, tid) || h.S != 6) continue;     // not RL-priced: the mid launch's regular path
         for (int k = tid; k < H; k += NT_CELL) {                  // the indoor-air chain (solve_direct, chain 0)
             const double wk = pow(h.gamma, (double)k) * D.price[k];
             D.cA[k] = h.aT;
-            D.cC[k] = D.oat[k + 1] * h.iR * 3600 * h.inv_c;
+            D.cC[k] = air_C(h, D.oat[k + 1]);
             D.cq[k] = wk * h.Pact;
         }
         __syncthreads();
@@ -5034,10 +5036,6 @@ size_t kernel_lds_bytes(const dragg_mpc_dims* d) {
     return direct_mode(d) ? (size_t)front_layout(d->horizon).bytes : (size_t)lds_doubles(d->horizon) * 8;
 }
 
-// the dynamic LDS limit the launches raise: the 160 KB of a CU less room for the kernels' static
-// LDS (the persistent launches' take slot)
-constexpr int LDS_DYN_MAX = 160 * 1024 - 256;
-
 int check_dims(const dragg_mpc_dims* d) {
     if (!d || d->n_homes < 0 || d->horizon < 1 || d->sub_steps < 1 || d->dt < 1) return DRAGG_E_ARG;
     if (d->n_homes > HOME_MASK) return DRAGG_E_ARG;                   // the deferred lists' home field
@@ -5047,7 +5045,7 @@ int check_dims(const dragg_mpc_dims* d) {
     if (direct_mode(d) && d->sub_steps > 15) return DRAGG_E_ARG;     // 4-bit duty in the DP record
     if (direct_mode(d) && !direct_fits(d->horizon)) return DRAGG_E_HORIZON;
     if (kernel_lds_bytes(d) > LDS_DYN_MAX) return DRAGG_E_HORIZON;
-    if (direct_mode(d) && big_layout(d->horizon, d->sub_steps).bytes > LDS_DYN_MAX) return DRAGG_E_HORIZON;
+    if (direct_mode(d) && second_layout<BigDP>(d->horizon, d->sub_steps).bytes > LDS_DYN_MAX) return DRAGG_E_HORIZON;
     if (direct_mode(d) && narrow_layout(d->horizon, d->sub_steps).bytes > LDS_DYN_MAX) return DRAGG_E_HORIZON;
     return DRAGG_OK;
 }
@@ -5139,8 +5137,8 @@ Launches launches(const dragg_mpc_dims& d, int nw = 1, int ilp = 1) {
             {hot, nw * WAVE, lds},
             {(const void*)side_front_kernel, WAVE, lds},
             {(const void*)cell_kernel<PM == PM_GROUPED ? PM_GROUPED : PM_STEP>, NT_CELL, (size_t)cell_lds_bytes(H)},
-            {(const void*)mpc_direct_kernel<PM, DM_MID, NW_MID>, NW_MID * WAVE, (size_t)mid_layout(H, S).bytes},
-            {(const void*)mpc_direct_kernel<PM, DM_BUCKET, NW_BIG>, NW_BIG * WAVE, (size_t)big_layout(H, S).bytes},
+            {(const void*)mpc_direct_kernel<PM, DM_MID, NW_MID>, NW_MID * WAVE, (size_t)second_layout<MidDP>(H, S).bytes},
+            {(const void*)mpc_direct_kernel<PM, DM_BUCKET, NW_BIG>, NW_BIG * WAVE, (size_t)second_layout<BigDP>(H, S).bytes},
             {(const void*)mpc_direct_kernel<PM, DM_NARROW, NT_STEPS / WAVE>, NT_STEPS,
              (size_t)narrow_layout(H, S, knobs().narrow_lds).bytes}};
 }

@@ -222,6 +222,66 @@ def test_size_queries_without_gpu(lib_path):
     assert lib.dragg_mpc_lds_bytes(ctypes.byref(d)) == -4
 
 
+def _round_dims(L, N, H, S=6, n_rp=1, int_mode=None):
+    return L.Dims(n_homes=N, horizon=H, sub_steps=S, dt=4, n_draw_hours=48, n_env=0, n_rp=n_rp,
+                  int_mode=L.INT_ROUND if int_mode is None else int_mode, max_iter=0, check_every=0, discount=0.92)
+
+
+# H -> hot launch LDS, workspace, workspace with a reward-price list (cell rows), side workspace; N = 100, S = 6,
+# round mode: the values of the build before the LDS layouts were written once
+PINNED_SIZES = {1: (9712, 314328576, 314328576, 314050048),
+                17: (10736, 375864832, 379551232, 372770304),
+                48: (12720, 495091200, 505126400, 486540800),
+                96: (16928, 679699968, 699565568, 662701568),
+                143: (23120, 860462848, 889954048, 835192320)}
+
+
+@pytest.mark.parametrize("H", sorted(PINNED_SIZES))
+def test_pinned_size_queries(lib_path, H):
+    from dragg_amd import _lib as L
+    lib = L.load()
+    d, dc = _round_dims(L, 100, H), _round_dims(L, 100, H, n_rp=H)
+    got = (lib.dragg_mpc_lds_bytes(ctypes.byref(d)), lib.dragg_mpc_workspace_bytes(ctypes.byref(d)),
+           lib.dragg_mpc_workspace_bytes(ctypes.byref(dc)), lib.dragg_mpc_side_workspace_bytes(ctypes.byref(d)))
+    assert got == PINNED_SIZES[H]
+
+
+def _largest_horizon(L, S, int_mode):
+    lib = L.load()
+    ok = [H for H in range(1, 200) if lib.dragg_mpc_lds_bytes(ctypes.byref(_round_dims(L, 100, H, S=S, int_mode=int_mode))) > 0]
+    assert ok == list(range(1, len(ok) + 1))             # accepted up to a largest horizon, none past it
+    return ok[-1]
+
+
+def test_largest_accepted_horizons(lib_path):
+    from dragg_amd import _lib as L
+    lib = L.load()
+    for S in (1, 4, 6, 7, 8, 12, 15):
+        assert _largest_horizon(L, S, L.INT_ROUND) == 159
+        assert lib.dragg_mpc_lds_bytes(ctypes.byref(_round_dims(L, 100, 160, S=S))) == -4
+    assert _largest_horizon(L, 6, L.INT_RELAX) == 69
+    assert _largest_horizon(L, 6, L.INT_ROUND_LP) == 69
+
+
+@pytest.mark.parametrize("N,H", [(5, 24), (100, 48), (1000, 96)])
+@pytest.mark.parametrize("cells", [False, True])
+def test_workspace_regions_match_the_library(lib_path, N, H, cells):
+    """dragg_amd._lib.workspace_regions against the library's two size queries (totals and the side span do
+    not prove the order of the regions: tests/test_gpu_workspace_regions.py reads the lists)."""
+    from dragg_amd import _lib as L
+    lib = L.load()
+    d = _round_dims(L, N, H, n_rp=H if cells else 1)
+    r = L.workspace_regions(N, H, cells)
+    assert r["total"] == lib.dragg_mpc_workspace_bytes(ctypes.byref(d))
+    assert r["w_rows"] - r["deferred"] == lib.dragg_mpc_side_workspace_bytes(ctypes.byref(d))
+    keys = list(r)
+    assert keys == ["back_pointers", "solutions", "deferred", "big_rows", "steps_list", "steps_pools", "mid_list",
+                    "mid_rows", "w_rows", "cell_rows", "total"]
+    assert all(r[a] <= r[b] for a, b in zip(keys, keys[1:]))
+    assert all(r[k] % 256 == 0 for k in keys[keys.index("deferred") + 1:-1])
+    assert r["solutions"] % 256 == 0
+
+
 def test_side_grid_clamped_to_scratch_slots(lib_path, monkeypatch):
     """DRAGG_SIDE_GRID entries are clamped to each side launch's per-block scratch: the
     step-function launch's narrow_slots(N) = min(N, 16) pools, the big launch's 512 and the mid launch's

@@ -31,8 +31,7 @@ total = bargs.warmup + bargs.steps
 agg = DeviceAggregator(homes, oat, ghi, tou, 0, total, reward_price=[0.0], int_mode=bargs.int_mode, seed=12,
                        keep_history=not bargs.no_history)
 N, H = agg.batch.N, agg.batch.H
-NBC = 336                                      # NB_CAP: the back-pointer rows before the solutions
-par = ((N * H * NBC * 2 + 255) // 256) * 256
+par = L.workspace_regions(N, H)["solutions"]   # (the back-pointer rows come before the solutions)
 kids_tot, fT, fW, n_ran = 0.0, [], [], 0
 for t in range(total):
     agg.run_iteration()

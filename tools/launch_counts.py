@@ -11,23 +11,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from dragg_amd._lib import workspace_regions                        # noqa: E402
 from dragg_amd.aggregator import DeviceAggregator                   # noqa: E402
 from dragg_amd.community import synthetic_homes, synthetic_weather  # noqa: E402
-
-
-def offsets(N, H):
-    """mpc_kernel.hip's workspace layout (par_region_bytes ... mid_list_offset)."""
-    r = lambda x: (x + 255) // 256 * 256  # noqa: E731
-    par = r(N * H * 336 * 2)
-    defer = par + N * 8 * H * 8
-    w_off = r(defer + (N + 2) * 4)
-    big = r(w_off + N * (H + 1) * 64 * 16)
-    nl = r(big + 512 * H * 2048 * 2)
-    slot = (2 * (H + 1) * 16384 + 2 * 16 * 16385) * 8 + (16 + 16 * 15) * 16385 * 4
-    nr = r(nl + (N + 2) * 4)
-    ml = r(nr + 8 * slot)
-    return defer, ml, nl
-
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--homes", type=int, default=10000)
@@ -40,7 +26,8 @@ homes = synthetic_homes(a.homes, seed=12, days=days, dt=dt, horizon_hours=hh)
 oat, ghi, tou = synthetic_weather(days, dt, math.ceil(a.steps / dt), seed=3, month=7)
 agg = DeviceAggregator(homes, oat, ghi, tou, 0, a.steps, reward_price=[0.0], seed=12, keep_history=False)
 N, H = agg.batch.N, agg.batch.H
-offs = offsets(N, H)
+regions = workspace_regions(N, H)
+offs = [regions[k] for k in ("deferred", "mid_list", "steps_list")]
 rng = np.random.default_rng(5)
 tot = np.zeros(3, int)
 for t in range(a.steps):

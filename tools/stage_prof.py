@@ -31,7 +31,7 @@ oat, ghi, tou = synthetic_weather(days, dt, math.ceil(a.steps / dt), seed=3, mon
 agg = DeviceAggregator(homes, oat, ghi, tou, 0, a.steps, reward_price=[0.0], seed=12, keep_history=False,
                        rank=a.rank, world=a.world)
 N, H = agg.batch.N, agg.batch.H
-par = ((N * H * 336 * 2 + 255) // 256) * 256
+par = L.workspace_regions(N, H)["solutions"]
 acc = []
 for t in range(a.steps):
     agg.run_iteration()

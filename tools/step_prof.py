@@ -28,7 +28,7 @@ homes = synthetic_homes(a.homes, seed=12, days=days, dt=dt, horizon_hours=hh)
 oat, ghi, tou = synthetic_weather(days, dt, math.ceil(a.steps / dt), seed=3, month=7)
 agg = DeviceAggregator(homes, oat, ghi, tou, 0, a.steps, reward_price=[0.0], seed=12, keep_history=False)
 N, H = agg.batch.N, agg.batch.H
-par = ((N * H * 336 * 2 + 255) // 256) * 256
+par = L.workspace_regions(N, H)["solutions"]
 rows = []
 names = ["feas", "lpdom", "cutpass", "recov", "sum_np", "max_np", "global", "flags", "sum_Mc", "ub_ext", "ub", "ranges", "-", "compact", "vstage", "merge", "values"]
 for t in range(a.steps):
