@@ -80,6 +80,11 @@ class Explicit(ctypes.Structure):
                 ("draw", c_dp), ("oat", c_dp), ("ghi", c_dp), ("price", c_dp)]
 
 
+class Episodes(ctypes.Structure):
+    """dragg_mpc_episodes: the groups' own seeds (uint64), start indices and timesteps (int32), each [G]."""
+    _fields_ = [("seed", c_dp), ("start_index", c_dp), ("timestep", c_dp)]
+
+
 class Lag(ctypes.Structure):
     _fields_ = [("clock", c_dp), ("skipped", c_dp), ("narrow", c_dp), ("side_workspace", c_dp)]
 
@@ -129,7 +134,8 @@ EXPORTS = ["dragg_mpc_abi_version", "dragg_mpc_strerror", "dragg_mpc_lds_bytes",
            "dragg_mpc_solve_explicit", "dragg_mpc_aggregate", "dragg_mpc_season_noise", "dragg_mpc_reload_knobs",
            "dragg_mpc_lag_reset", "dragg_mpc_step_main", "dragg_mpc_step_side", "dragg_mpc_aggregate_rows",
            "dragg_mpc_side_workspace_bytes", "dragg_mpc_side_grid", "dragg_mpc_source_hash",
-           "dragg_mpc_replicate", "dragg_mpc_aggregate_groups"]
+           "dragg_mpc_replicate", "dragg_mpc_aggregate_groups", "dragg_mpc_step_episodes",
+           "dragg_mpc_season_noise_episodes"]
 
 _LIB = None
 
@@ -190,6 +196,10 @@ def load(path=LIB_PATH):
     lib.dragg_mpc_aggregate_rows.argtypes = [ctypes.POINTER(Dims), c_dp, ctypes.c_int32, c_dp, c_dp]
     lib.dragg_mpc_replicate.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Hash), ctypes.POINTER(Hash), c_dp]
     lib.dragg_mpc_aggregate_groups.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Hash), c_dp, c_dp]
+    lib.dragg_mpc_step_episodes.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Problem), ctypes.POINTER(Episodes),
+                                            ctypes.POINTER(Hash), ctypes.POINTER(Out), ctypes.c_int32, c_dp, c_dp]
+    lib.dragg_mpc_season_noise_episodes.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Episodes), ctypes.c_int32,
+                                                    ctypes.c_int32, ctypes.c_int32, c_dp, c_dp]
     if lib.dragg_mpc_abi_version() != ABI_VERSION:
         raise DraggError("ABI version mismatch between dragg_amd and libdragg_mi355x.so")
     if not os.environ.get("DRAGG_LIB"):

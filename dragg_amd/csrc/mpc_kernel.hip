@@ -1251,7 +1251,13 @@ DEV int write_fallback(const Home& h, const Lds& L, const Io& io, int status) {
 struct KArgs {
     dragg_mpc_dims d;
     dragg_mpc_problem p;
-    dragg_mpc_explicit ex;
+    // the inputs of the entry point's own, never both: explicit per-home inputs (PM_EXPLICIT kernels) or the
+    // groups' own seeds, start indices and clocks, each [G] or NULL: the shared value (PM_EPISODES kernels).
+    // One slot for both keeps the kernels' argument block, and with it the code of every other kernel, as it was
+    union {
+        dragg_mpc_explicit ex;
+        dragg_mpc_episodes ep;
+    };
     double* vals;
     double* fc;
     dragg_mpc_out out;
@@ -1270,6 +1276,7 @@ struct KArgs {
     long long step_work_cap;   // ... its work bound per pass (0: STEP_WORK_CAP)
     int narrow_lds;        // the step-function launch's LDS bytes per block (0: all a CU has, narrow_layout)
 };
+static_assert(sizeof(dragg_mpc_episodes) <= sizeof(dragg_mpc_explicit), "KArgs: ep shares ex's slot");
 
 // a clock value the side pass wrote: the reader must acquire before it reads the home's rows
 constexpr int LAG_SIDE = 1 << 30;
@@ -1295,7 +1302,35 @@ DEV void lag_finish(const KArgs& a, int home) {
 // PM, the prologue's mode (a template argument of every solve kernel; the host picks the instantiation, so
 // the kernels of an ordinary step carry no trace of the grouped indexing): the step's inputs from the
 // problem arrays, explicit per-home inputs (dragg_mpc_solve_explicit), or a step of a grouped batch
-constexpr int PM_STEP = 0, PM_EXPLICIT = 1, PM_GROUPED = 2;
+// (PM_GROUPED), or a step of a batch of episodes (PM_EPISODES, dragg_mpc_step_episodes: a grouped batch whose
+// groups each have their own noise seed, start index and clock)
+constexpr int PM_STEP = 0, PM_EXPLICIT = 1, PM_GROUPED = 2, PM_EPISODES = 3;
+
+// PM_EPISODES: the group of a home and the three values of its own.  The group is the same for the whole
+// block (taken from the first lane's home), so the loads are scalar
+struct Episode {
+    unsigned g, base;      // the home's group and its base home
+    int t, start;          // the group's timestep (< 0: idle) and start index
+    uint64_t seed;
+};
+DEV Episode episode_of(const KArgs& a, int home) {
+    const unsigned hs = (unsigned)__builtin_amdgcn_readfirstlane(home);
+    const unsigned nb = (unsigned)a.d.n_homes / (unsigned)max(a.d.n_groups, 1);
+    Episode e;
+    e.g = hs / nb;
+    e.base = hs - e.g * nb;
+    e.t = a.ep.timestep ? a.ep.timestep[e.g] : a.t;
+    e.start = a.ep.start_index ? a.ep.start_index[e.g] : a.p.start_index;
+    e.seed = a.ep.seed ? a.ep.seed[e.g] : a.p.seed;
+    return e;
+}
+// An idle group takes no part in the step: its clock is negative, or its window [start + t, start + t + H]
+// does not lie inside the environment lists (the host cannot see the device-resident clocks: the kernel
+// must not read past the lists)
+DEV bool episode_idle(const KArgs& a, const Episode& e) {
+    return e.t < 0 || e.start < 0 || (long long)e.start + e.t + a.d.horizon >= (long long)a.d.n_env;
+}
+
 template <int PM>
 DEV int prologue(const KArgs& a, Home& h, const Lds& L, const Io& io, int lane, int nt, double* red) {
     const int home = io.home;
@@ -1322,13 +1357,16 @@ DEV int prologue(const KArgs& a, Home& h, const Lds& L, const Io& io, int lane, 
         __syncthreads();
     } else {
 #pragma clang fp contract(off)   // draw sizes, Tw0 mixing and the season test as in numpy
-        const int t = a.t;
+        // (a batch of episodes: the group's own clock, start index and seed in place of the shared ones)
+        Episode ep{};
+        if (PM == PM_EPISODES) ep = episode_of(a, home);
+        const int t = PM == PM_EPISODES ? ep.t : a.t;
         h.t = t;
         const int dt = h.dt;
         const int lag = H / dt + 1;                           // mpc_calc.py:194
         const int nraw = lag * dt;
         const int base_hour = t / dt;
-        const int s0 = a.p.start_index + t;
+        const int s0 = (PM == PM_EPISODES ? ep.start : a.p.start_index) + t;
         // a grouped batch (dims.n_groups = G > 1: G consecutive replicas of N / G base homes): the home
         // reads its group's price row and draws its base home's noise.  Both are the same for the whole
         // block: computed from the first lane's home so that they stay in scalar registers
@@ -1340,6 +1378,10 @@ DEV int prologue(const KArgs& a, Home& h, const Lds& L, const Io& io, int lane, 
             const unsigned g = hs / nb;
             rpl += (size_t)g * a.d.n_rp;
             nhome = (int)(hs - g * nb);
+        }
+        if (PM == PM_EPISODES) {
+            rpl += (size_t)ep.g * a.d.n_rp;
+            nhome = (int)ep.base;
         }
         auto rawv = [&](int idx) -> double {                  // np.repeat(list, dt) / dt
             const int hh = base_hour + idx / dt - lag;
@@ -1364,7 +1406,7 @@ DEV int prologue(const KArgs& a, Home& h, const Lds& L, const Io& io, int lane, 
             if (a.noise) z = a.noise[(size_t)k * N + home];
             else {
                 double z0, z1;
-                normal_pair(a.p.seed, a.p.home_offset + nhome * max(a.p.home_stride, 1), t, k >> 1, &z0, &z1);
+                normal_pair(PM == PM_EPISODES ? ep.seed : a.p.seed, a.p.home_offset + nhome * max(a.p.home_stride, 1), t, k >> 1, &z0, &z1);
                 z = (k & 1) ? z1 : z0;
             }
             mx = fmax(mx, a.p.oat[s0 + k + 1] + pow(1.1, (double)k) * z);
@@ -1429,6 +1471,8 @@ __global__ __launch_bounds__(64) void mpc_home_kernel(KArgs a) {
     const int lane = threadIdx.x;
     const int N = a.d.n_homes;
     if (home >= N) return;
+    if constexpr (PM == PM_EPISODES)            // an idle group's blocks leave before any write
+        if (episode_idle(a, episode_of(a, home))) return;
     Home h;
     const int H = a.d.horizon;
     Lds L = carve(smem, H);
@@ -4801,6 +4845,10 @@ __global__ __launch_bounds__(WAVE * NW, MODE == DM_FRONT ? (ILP > 1 ? 2 : 3) : M
     if constexpr (MODE == DM_FRONT) {           // (the side pass's hot launch: side_front_kernel)
         const int home = blockIdx.x;
         if (home >= N) return;
+        // an idle group's blocks leave before any write; every later launch works off the lists this one
+        // fills, so none of them sees an idle home
+        if constexpr (PM == PM_EPISODES)
+            if (episode_idle(a, episode_of(a, home))) return;
         if (a.clk) {
             // lag mode, main pass: a home whose previous step is not complete yet goes to the side pass
             if (threadIdx.x == 0) take = __hip_atomic_load(a.clk + home, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -5015,6 +5063,23 @@ __global__ void noise_kernel(int N, int H, uint64_t seed, int off, int stride, i
     if (2 * pr + 1 < H) out[(size_t)(2 * pr + 1) * N + home] = z1;
 }
 
+// (a batch of episodes: home r of group g = r / nb draws the stream of (seed[g], its base home, timestep[g] --
+// NULL: t); the rows of a group whose timestep is negative are left as they are)
+__global__ void noise_episodes_kernel(int N, int H, dragg_mpc_episodes ep, int off, int stride, int t, double* out,
+                                      int nb) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int pairs = (H + 1) / 2;
+    if (idx >= N * pairs) return;
+    const int home = idx % N, pr = idx / N;
+    const int g = home / nb;
+    const int tg = ep.timestep ? ep.timestep[g] : t;
+    if (tg < 0) return;
+    double z0, z1;
+    normal_pair(ep.seed[g], off + (home - g * nb) * stride, tg, pr, &z0, &z1);
+    out[(size_t)(2 * pr) * N + home] = z0;
+    if (2 * pr + 1 < H) out[(size_t)(2 * pr + 1) * N + home] = z1;
+}
+
 // --------------------------------------------------------------------------------------
 // Host layer.  Sizes and check_dims; the knobs; one description per launch (struct Launch: kernel,
 // threads, LDS) run through `run`, which raises the kernel's LDS limit once per device; the launch
@@ -5136,7 +5201,7 @@ Launches launches(const dragg_mpc_dims& d, int nw = 1, int ilp = 1) {
     return {{(const void*)mpc_home_kernel<PM>, WAVE, lds},
             {hot, nw * WAVE, lds},
             {(const void*)side_front_kernel, WAVE, lds},
-            {(const void*)cell_kernel<PM == PM_GROUPED ? PM_GROUPED : PM_STEP>, NT_CELL, (size_t)cell_lds_bytes(H)},
+            {(const void*)cell_kernel<PM == PM_EXPLICIT ? PM_STEP : PM>, NT_CELL, (size_t)cell_lds_bytes(H)},
             {(const void*)mpc_direct_kernel<PM, DM_MID, NW_MID>, NW_MID * WAVE, (size_t)second_layout<MidDP>(H, S).bytes},
             {(const void*)mpc_direct_kernel<PM, DM_BUCKET, NW_BIG>, NW_BIG * WAVE, (size_t)second_layout<BigDP>(H, S).bytes},
             {(const void*)mpc_direct_kernel<PM, DM_NARROW, NT_STEPS / WAVE>, NT_STEPS,
@@ -5365,6 +5430,26 @@ int dragg_mpc_step(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, dr
     return a.d.n_groups > 1 ? launch<PM_GROUPED>(a, (hipStream_t)stream) : launch<PM_STEP>(a, (hipStream_t)stream);
 }
 
+// A step of a batch of episodes: dragg_mpc_step's launches with the PM_EPISODES kernels.  The shared
+// start_index and timestep are checked against the environment lists only where a group can read them (their
+// member array is NULL); the groups' own values live on the device and are checked there (episode_idle)
+int dragg_mpc_step_episodes(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, const dragg_mpc_episodes* ep,
+                            dragg_mpc_hash* hash, dragg_mpc_out* out, int32_t timestep, const double* noise,
+                            void* stream) {
+    if (!ep || !prob) return DRAGG_E_ARG;
+    if (dims && dims->n_homes >= 0 && dims->n_homes % max(dims->n_groups, 1) != 0) return DRAGG_E_ARG;
+    dragg_mpc_problem p = *prob;
+    if (ep->start_index) p.start_index = 0;
+    KArgs a;
+    const int rc = solve_args(dims, &p, hash, out, ep->timestep ? 0 : timestep, true, &a);
+    if (rc || dims->n_homes == 0) return rc;
+    a.p = *prob;
+    a.t = timestep;
+    a.noise = noise;
+    a.ep = *ep;
+    return launch<PM_EPISODES>(a, (hipStream_t)stream);
+}
+
 // one pass of a lag-mode step: solve_args, then what only lag mode needs
 static int step_lag(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, dragg_mpc_hash* hash,
                     dragg_mpc_out* out, int32_t timestep, const dragg_mpc_lag* lag, bool side, void* stream) {
@@ -5479,6 +5564,20 @@ int dragg_mpc_season_noise(const dragg_mpc_dims* dims, uint64_t seed, int32_t ho
     hipLaunchKernelGGL(noise_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                        dims->n_homes, dims->horizon, seed, home_offset, max(home_stride, 1), timestep, noise_out,
                        dims->n_homes / max(dims->n_groups, 1));
+    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+}
+
+int dragg_mpc_season_noise_episodes(const dragg_mpc_dims* dims, const dragg_mpc_episodes* ep, int32_t home_offset,
+                                    int32_t home_stride, int32_t timestep, double* noise_out, void* stream) {
+    if (!dims || dims->n_homes < 0 || dims->horizon < 1 || dims->n_groups < 0 || !ep) return DRAGG_E_ARG;
+    const int G = max(dims->n_groups, 1);
+    if (dims->n_homes % G != 0) return DRAGG_E_ARG;
+    const int total = dims->n_homes * ((dims->horizon + 1) / 2);
+    if (total == 0) return DRAGG_OK;
+    if (!noise_out || !ep->seed) return DRAGG_E_ARG;           // (no problem struct here: no shared seed)
+    hipLaunchKernelGGL(noise_episodes_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                       dims->n_homes, dims->horizon, *ep, home_offset, max(home_stride, 1), timestep, noise_out,
+                       dims->n_homes / G);
     return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
 }
 

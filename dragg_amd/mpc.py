@@ -421,6 +421,52 @@ class MPCBatch:
                        L.ptr(out), stream=stream)
             return out
 
+    # ------------------------------------------------------------------ vectorised episodes
+    def _episodes(self, seeds, starts, clocks):
+        """The dragg_mpc_episodes struct of device tensors [G] (None: the member stays NULL, the shared
+        value for every group) and the tensors it points to."""
+        G, dev = self.groups, self.device
+
+        def member(x, dtypes, name):
+            if x is None:
+                return None
+            if not torch.is_tensor(x) or x.device != dev or x.dtype not in dtypes or tuple(x.shape) != (G,) \
+                    or not x.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous device tensor [{G}] of {dtypes[0]}, not "
+                                 f"{getattr(x, 'dtype', type(x))} {list(getattr(x, 'shape', []))}")
+            return x
+        keep = (member(seeds, (torch.int64, getattr(torch, "uint64", torch.int64)), "seeds"), member(starts, (torch.int32,), "starts"),
+                member(clocks, (torch.int32,), "clocks"))
+        return L.Episodes(seed=L.ptr(keep[0]), start_index=L.ptr(keep[1]), timestep=L.ptr(keep[2])), keep
+
+    def step_episodes(self, seeds, starts, clocks, noise=None, hist=None, stream=None, t=0):
+        """One step of a batch of episodes (dragg_mpc_step_episodes): group g with its own season-noise
+        seed `seeds[g]` (int64 / uint64 [G], the bits are the key), start index `starts[g]` and timestep
+        `clocks[g]` (int32 [G]; negative: the group is idle and nothing of it is written), all device
+        tensors read by the kernels -- no host synchronisation.  None for any of them: the batch's own
+        seed / start_index / `t` for every group."""
+        with torch.cuda.device(self.device):
+            ep, keep = self._episodes(seeds, starts, clocks)
+            if noise is not None:
+                noise = noise.to(device=self.device, dtype=torch.float64).contiguous()
+                assert tuple(noise.shape) == (self.H, self.N)
+            self._call(self.lib.dragg_mpc_step_episodes, self._problem(), ep, self._hash(), self._out(hist), int(t),
+                       L.ptr(noise), stream=stream)
+            self._keep = (noise, hist, keep)
+            return self.status
+
+    def season_noise_episodes(self, seeds, clocks, out=None, stream=None, t=0):
+        """The keyed season draw [H][N] of a batch of episodes (dragg_mpc_season_noise_episodes): group g
+        draws the stream of (seeds[g], base home, clocks[g]); an idle group's columns keep `out`'s values
+        (NaN in a fresh tensor)."""
+        with torch.cuda.device(self.device):
+            ep, keep = self._episodes(seeds, None, clocks)
+            if out is None:
+                out = torch.full((self.H, self.N), float("nan"), dtype=torch.float64, device=self.device)
+            self._call(self.lib.dragg_mpc_season_noise_episodes, ep, self.home_offset, self.home_stride, int(t),
+                       L.ptr(out), stream=stream)
+            self._keep = (keep, out)
+            return out
 
     # ------------------------------------------------------------------ hash views
     def hash_dict(self, i, as_str=True):

@@ -5,6 +5,9 @@ community solve of 10^4-10^5 homes on the GPU.  What a policy needs from the com
 aggregate load, its forecast, the setpoint and candidate-price rollouts -- comes from
 `dragg_amd.runner.Aggregator` (`rl_step`, `rl_forecast`, `rl_sweep`, `collect_data`), i.e. from
 device-resident solves; `rl_sweep` solves G candidate prices in one grouped launch (`SweepAgent`).
+`VectorEnv` (`Aggregator.rl_vector`) steps E independent episodes of the community as one batch, each
+with its own seed, start index, clock and price, for policies that learn over many episodes
+(`SetpointAgent.train_vector`).
 
 The reference's learning agent (`dragg/agent.py`, an abstract actor-critic whose
 `calc_state` / `reward` are left to a subclass and which no driver of v1 calls) is out of
@@ -18,6 +21,27 @@ none): a discrete PI controller on the relative forecast error against the aggre
 setpoint (`gen_setpoint`, aggregator.py:677-696), clipped to `rl.utility.action_space`.
 """
 import numpy as np
+
+
+def setpoint_update(state, timestep, agg_load, max_poss_load, prev_timesteps):
+    """`Aggregator.gen_setpoint`'s rule (aggregator.py:677-696), once, for the runner and for every
+    episode of a `VectorEnv`.  `state` is (tracked_loads, max_load, min_load) of the previous call, or
+    None before the first; at timestep < 2 the tracked loads start over at half the community's maximum
+    possible load, later the oldest makes room for `agg_load`.  -> (tracked_loads, max_load, min_load,
+    avg_load); the setpoint is avg_load.  `prev_timesteps` is read only when the loads start over."""
+    if timestep < 2 or state is None:
+        tracked = [0.5 * max_poss_load] * prev_timesteps
+        max_load, min_load = -float("inf"), float("inf")
+    else:
+        tracked, max_load, min_load = state
+        tracked[:-1] = tracked[1:]
+        tracked[-1] = agg_load
+    avg_load = np.average(tracked)
+    if agg_load > max_load or timestep % 24 == 0:
+        max_load = agg_load
+    if agg_load < min_load or timestep % 24 == 0:
+        min_load = agg_load
+    return tracked, max_load, min_load, avg_load
 
 
 def policy_from_agent(agent, scale=1.0):
@@ -62,6 +86,122 @@ class SetpointAgent:
     def act(self, env):
         """policy(aggregator) -> reward price for `Aggregator.run_rl_agg`."""
         return self.train(env) / self.scale
+
+    def train_vector(self, env_obs):
+        """`train` for the E episodes of a `VectorEnv` at once: E independent PI states (`integral_v`),
+        each exactly the scalar controller on its episode's observation.  `env_obs`: the environment's
+        observations (`forecast_load` and `agg_setpoint`, [E] each).  -> actions [E]."""
+        f = np.asarray(env_obs["forecast_load"], dtype=float)
+        s = np.asarray(env_obs["agg_setpoint"], dtype=float)
+        sp = np.where(s != 0, s, 1.0)
+        e = (f - sp) / sp
+        if getattr(self, "integral_v", None) is None or len(self.integral_v) != len(e):
+            self.integral_v = np.zeros(len(e))
+        if self.ki:
+            self.integral_v = np.clip(self.integral_v + e, self.lo / self.ki, self.hi / self.ki)
+        a = np.clip(self.kp * e + self.ki * self.integral_v, self.lo, self.hi)
+        self.history["error"].append(e.tolist())
+        self.history["action"].append(a.tolist())
+        return a
+
+    def reset_vector(self, mask=None):
+        """Clear the PI state of the masked episodes (default: all), e.g. when they start over."""
+        if getattr(self, "integral_v", None) is not None:
+            self.integral_v = np.where(np.ones(len(self.integral_v), bool) if mask is None
+                                       else np.asarray(mask, dtype=bool), 0.0, self.integral_v)
+
+    def act_vector(self, env_obs):
+        """Observations -> reward prices [E] for `VectorEnv.step`."""
+        return self.train_vector(env_obs) / self.scale
+
+
+class VectorEnv:
+    """E episodes of one community as a vector environment for reward-price policies, on a
+    `dragg_amd.vector.VectorAggregator`.
+
+    reset() -> observations; step(actions [E] or [E][n]: each episode's reward price in $/kWh) ->
+    (observations, done [E]).  An observation holds, per episode ([E] numpy arrays): `agg_load`,
+    `forecast_load`, `agg_cost` (collect_data's sums of its last step), `agg_setpoint` and `timestep`.
+    The setpoint is `Aggregator.gen_setpoint`'s rule (`setpoint_update`: tracked loads,
+    `agg.rl.prev_timesteps`, the community's maximum possible load), kept per episode in the order of
+    `Aggregator.setup_rl_agg_run` / `rl_step`.  An episode that has run its `num_timesteps` steps is done
+    and sits idle until it is reset (`reset(mask)`); parked episodes sit idle too.  The three sums come to
+    the host once per step (the policies are host code)."""
+
+    def __init__(self, vector_aggregator, config, max_poss_load=None, n_homes=None):
+        from . import inputs as I
+        self.va = va = vector_aggregator
+        self.config = config
+        self.E, self.T = va.E, va.num_timesteps
+        self.prev_timesteps = config["agg"]["rl"]["prev_timesteps"]
+        self.max_poss_load = (sum(I.max_load(h) for h in va.homes) if max_poss_load is None else max_poss_load)
+        self.n_homes = va.Nb if n_homes is None else int(n_homes)
+        self.timestep = np.zeros(self.E, dtype=np.int64)
+        self.parked = np.zeros(self.E, dtype=bool)
+        self.agg_load = np.zeros(self.E)
+        self.forecast_load = np.zeros(self.E)
+        self.agg_cost = np.zeros(self.E)
+        self.agg_setpoint = np.zeros(self.E)
+        self._sp = [None] * self.E
+
+    def _host_mask(self, mask):
+        if mask is None:
+            return np.ones(self.E, dtype=bool)
+        a = np.asarray(mask.cpu() if hasattr(mask, "cpu") else mask)
+        if a.dtype != bool:
+            m = np.zeros(self.E, dtype=bool)
+            m[a.reshape(-1).astype(np.int64)] = True
+            a = m
+        return a
+
+    def _setpoint(self, e):
+        st = setpoint_update(self._sp[e], int(self.timestep[e]), float(self.agg_load[e]), self.max_poss_load,
+                             self.prev_timesteps)
+        self._sp[e] = st[:3]
+        self.agg_setpoint[e] = st[3]
+
+    def observations(self):
+        return {"agg_load": self.agg_load.copy(), "forecast_load": self.forecast_load.copy(),
+                "agg_cost": self.agg_cost.copy(), "agg_setpoint": self.agg_setpoint.copy(),
+                "timestep": self.timestep.copy()}
+
+    def reset(self, mask=None, seeds=None, start_indices=None):
+        """Start the masked episodes (default: all) over, as `setup_rl_agg_run` starts a run: the load
+        and its forecast at 3 kW per home of the community, the setpoint from fresh tracked loads."""
+        m = self._host_mask(mask)
+        self.va.reset(None if mask is None else m, seeds=seeds, start_indices=start_indices)
+        for e in np.flatnonzero(m):
+            self.timestep[e] = 0
+            self.parked[e] = False
+            self.forecast_load[e] = self.agg_load[e] = 3 * self.n_homes
+            self.agg_cost[e] = 0.0
+            self._sp[e] = None
+            self._setpoint(e)
+        return self.observations()
+
+    def park(self, mask):
+        m = self._host_mask(mask)
+        self.va.park(m)
+        self.parked |= m
+
+    def resume(self, mask):
+        m = self._host_mask(mask)
+        self.va.resume(m)
+        self.parked &= ~m
+
+    def done(self):
+        return self.timestep >= self.T
+
+    def step(self, actions):
+        """Publish each episode's reward price, solve every active episode in one batch, collect, new
+        setpoints (the order of `Aggregator.rl_step`).  -> (observations, done [E])."""
+        on = ~self.parked & ~self.done()
+        agg = self.va.step(actions).cpu().numpy()
+        for e in np.flatnonzero(on):
+            self.timestep[e] += 1
+            self.agg_load[e], self.forecast_load[e], self.agg_cost[e] = agg[e]
+            self._setpoint(e)
+        return self.observations(), self.done()
 
 
 class SweepAgent:

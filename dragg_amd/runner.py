@@ -199,19 +199,36 @@ class Aggregator:
     # ------------------------------------------------------------------ RL aggregator (§8 F4)
     # aggregator.py:677-696
     def gen_setpoint(self):
-        if self.timestep < 2:
-            self.tracked_loads = [0.5 * self.max_poss_load] * self.config["agg"]["rl"]["prev_timesteps"]
-            self.max_load = -float("inf")
-            self.min_load = float("inf")
-        else:
-            self.tracked_loads[:-1] = self.tracked_loads[1:]
-            self.tracked_loads[-1] = self.agg_load
-        self.avg_load = np.average(self.tracked_loads)
-        if self.agg_load > self.max_load or self.timestep % 24 == 0:
-            self.max_load = self.agg_load
-        if self.agg_load < self.min_load or self.timestep % 24 == 0:
-            self.min_load = self.agg_load
+        # (the rule itself: rl.setpoint_update, shared with the per-episode setpoints of rl.VectorEnv)
+        from .rl import setpoint_update
+        fresh = self.timestep < 2
+        state = None if fresh else (self.tracked_loads, self.max_load, self.min_load)
+        self.tracked_loads, self.max_load, self.min_load, self.avg_load = setpoint_update(
+            state, self.timestep, self.agg_load, self.max_poss_load,
+            self.config["agg"]["rl"]["prev_timesteps"] if fresh else None)
         return self.avg_load
+
+    def rl_vector(self, episodes, seeds=None, start_indices=None):
+        """A vector environment of `episodes` independent runs of the loaded community (`get_homes`), all
+        stepped as one grouped batch (dragg_amd.vector.VectorAggregator, rl.VectorEnv): default seeds
+        `simulation.random_seed + e`, default start indices the config's own.  One rank only."""
+        from .rl import VectorEnv
+        from .vector import VectorAggregator
+        if self.world > 1:
+            raise ValueError("rl_vector runs on one rank: episodes are not sharded over ranks")
+        if not hasattr(self, "start_hour_index"):
+            self.flush()
+        E = int(episodes)
+        seed = int(self.config["simulation"]["random_seed"])
+        checked = [h for h in self.all_homes if self.check_type == "all" or h["type"] == self.check_type]
+        col = lambda c: self.all_data[c].to_numpy(dtype=float)  # noqa: E731
+        va = VectorAggregator(checked, col("OAT"), col("GHI"), col("tou"), E,
+                              [seed + e for e in range(E)] if seeds is None else seeds,
+                              [self.start_hour_index] * E if start_indices is None else start_indices,
+                              self.num_timesteps, int_mode=self.int_mode, device=self.device,
+                              **({"batch_cls": self.batch_cls} if self.batch_cls else {}))
+        return VectorEnv(va, self.config, max_poss_load=sum(I.max_load(h) for h in self.all_homes),
+                         n_homes=len(self.all_homes))
 
     # aggregator.py:664-675: the reward price goes to every rank's solver (RCCL broadcast from
     # rank 0) instead of the redis 'reward_price' list

@@ -328,6 +328,41 @@ int dragg_mpc_replicate(const dragg_mpc_dims* dims, const dragg_mpc_hash* src_ha
 int dragg_mpc_aggregate_groups(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, double* out,
                                void* stream);
 
+/* Vectorised episodes: a grouped batch (dims.n_groups = G, G >= 1 here) whose every group is a full episode
+   of the base community, with its own season-noise seed, its own start index into the environment lists
+   and its own clock.  Home r is in group g = r / Nb and has base home b = r % Nb; its step is exactly
+   dragg_mpc_step of base home b with seed ep.seed[g] (global home home_offset + b * home_stride),
+   start_index ep.start_index[g], timestep ep.timestep[g] and reward-price row g -- nothing else changes, so
+   group g equals, bit for bit, a plain batch of the Nb base homes run with those values.  The clock is per
+   group: one group may be at t = 0 and take its initial conditions from params while another reads its
+   hash arrays.  A NULL member means the shared value (problem.seed, problem.start_index, the `timestep`
+   argument) for every group; with all three NULL the step is dragg_mpc_step's.  An explicit `noise` array
+   ([H][N]) is used as given.
+   Idle groups: a group whose timestep is negative takes no part in the step -- its blocks return before any
+   write, so none of its columns changes in vals, fc, status, iters, obj, relax_obj, int_path or out.hist, and
+   none of its homes enters a later launch.  A group whose window [start_index + timestep, ... + horizon] does
+   not lie inside the environment lists (start_index < 0 or start_index + timestep + horizon >= n_env) is
+   idle too: the values live on the device, where only the kernel can check them.
+   The state persists in the hash arrays from step to step like any batch's; the caller advances the clocks.
+   Per-group sums: dragg_mpc_aggregate_groups; state fan-out: dragg_mpc_replicate.  Returns DRAGG_E_ARG for
+   ep == NULL or n_homes % G != 0.  dragg_mpc_solve_explicit and lag mode stay refused for G > 1. */
+typedef struct dragg_mpc_episodes {      /* all device pointers, [G], G = max(dims.n_groups, 1) */
+    const uint64_t* seed;         /* group g's season-noise seed     (NULL: problem.seed for all)        */
+    const int32_t*  start_index;  /* group g's start_hour_index      (NULL: problem.start_index)         */
+    const int32_t*  timestep;     /* group g's own timestep; < 0: the group is idle (NULL: `timestep`)   */
+} dragg_mpc_episodes;
+int dragg_mpc_step_episodes(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob,
+                            const dragg_mpc_episodes* ep, dragg_mpc_hash* hash, dragg_mpc_out* out,
+                            int32_t timestep, const double* noise, void* stream);
+
+/* The keyed season-noise stream of a batch of episodes: writes [H][N] normals, home r drawing the stream of
+   (ep.seed[g], global home home_offset + (r % Nb) * home_stride, ep.timestep[g]) -- ep.timestep NULL: the
+   `timestep` argument; ep.seed must be given (there is no shared seed here); ep.start_index is not read.  The
+   columns of an idle group (timestep < 0) are left as they are. */
+int dragg_mpc_season_noise_episodes(const dragg_mpc_dims* dims, const dragg_mpc_episodes* ep,
+                                    int32_t home_offset, int32_t home_stride, int32_t timestep,
+                                    double* noise_out, void* stream);
+
 /* Lag mode (since v8): run_rbo_mpc's timestep loop (aggregator.py:757-778) has no feedback between
    homes, so a home whose chain needs the slow exact step-function DP need not hold up the others.
    A step is split into two passes the caller puts on two streams:
