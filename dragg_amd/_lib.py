@@ -7,6 +7,8 @@ entry point raises.
 import ctypes
 import os
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 # DRAGG_LIB: an alternative build of the same library (kernel experiments); default in-tree
 LIB_PATH = os.environ.get("DRAGG_LIB") or os.path.join(HERE, "libdragg_mi355x.so")
@@ -232,6 +234,41 @@ def kernel_info(dims):
     return {LAUNCH_NAMES[i]: {"vgprs": info.vgprs[i], "scratch_bytes_per_lane": info.scratch_bytes[i],
                               "lds_bytes": info.lds_bytes[i], "threads": info.threads[i],
                               "blocks_per_cu": info.blocks_per_cu[i]} for i in range(NLAUNCH)}
+
+
+PATH_COUNT_KEYS = ("approx_solves", "step_dp_solves", "later_launch_solves")
+
+
+def path_counts(paths, dim=None):
+    """The solves of an int_path tensor by kind, stacked in the order of PATH_COUNT_KEYS (bits 0-11 set, solved
+    by the step-function DP, finished by a later launch), summed over `dim` (None: everything) -> int64 [3][...]."""
+    import torch
+    hits = [(paths & m) != 0 for m in (PATH_APPROX_MASK, PATH_STEPS, PATH_SECOND)]
+    return torch.stack([h.sum() if dim is None else h.sum(dim) for h in hits])
+
+
+def device_f64(x, device):
+    """Host values (a list, a numpy array) or a tensor of any dtype, wherever it lives -> a float64 tensor on
+    `device` (a tensor already there: no host round trip)."""
+    import torch
+    x = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=float))
+    return x.detach().to(device=device, dtype=torch.float64)
+
+
+def episode_mask(mask, E):
+    """None (every episode), a bool sequence / array / tensor [E], or episode indices -> bool [E]: a bool
+    tensor as it is (wherever it lives: no host round trip), anything else as a numpy array."""
+    if mask is None:
+        return np.ones(E, dtype=bool)
+    m = mask
+    if str(getattr(mask, "dtype", "")) != "torch.bool":
+        m = np.asarray(mask.cpu() if hasattr(mask, "cpu") else mask)
+        if m.dtype != bool:
+            idx, m = m.reshape(-1).astype(np.int64), np.zeros(E, dtype=bool)
+            m[idx] = True
+    if tuple(m.shape) != (E,):
+        raise ValueError(f"a mask of {E} episodes, not {list(m.shape)}")
+    return m
 
 
 def check(rc):

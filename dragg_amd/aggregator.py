@@ -163,13 +163,10 @@ class DeviceAggregator:
         solves finished by the mid / big / step-function launches (bit 12)}, over every rank."""
         self.drain()
         hi = self.timestep if hi is None else hi
-        p = self.path_hist[lo:hi]
-        v = torch.stack([((p & L.PATH_APPROX_MASK) != 0).sum(), ((p & L.PATH_STEPS) != 0).sum(),
-                         ((p & L.PATH_SECOND) != 0).sum()]).to(torch.int64)
+        v = L.path_counts(self.path_hist[lo:hi])
         if self.world > 1:
             torch.distributed.all_reduce(v, group=self.group)
-        a, s, m = (int(x) for x in v.cpu().tolist())
-        return {"approx_solves": a, "step_dp_solves": s, "later_launch_solves": m}
+        return dict(zip(L.PATH_COUNT_KEYS, v.cpu().tolist()))
 
     def approx_solves(self):
         """[(timestep, global home index, int_path)] of this shard's approximate solves so far."""
@@ -241,8 +238,7 @@ class DeviceAggregator:
     def set_reward_price(self, rp, src=0):
         """Broadcast the reward-price list decided on rank `src` (the RL agent's host) to every
         rank (one RCCL broadcast of action_horizon*dt fp64) and hand it to the solver."""
-        t = torch.as_tensor(np.asarray(rp, dtype=float) if not torch.is_tensor(rp) else rp,
-                            dtype=torch.float64).to(self.device).reshape(-1).contiguous()
+        t = L.device_f64(rp, self.device).reshape(-1).contiguous()
         if self.world > 1:
             torch.distributed.broadcast(t, src=src, group=self.group)
         self.batch.set_reward_price(t)
@@ -310,8 +306,7 @@ class DeviceAggregator:
         H = 48 and G = 8 under a price list 15.4 GB of workspace and 0.47 GB of hash arrays
         (profiles/r07/sweep/sweep_line.json)."""
         self.drain()
-        P = torch.as_tensor(np.asarray(prices, dtype=float) if not torch.is_tensor(prices) else prices,
-                            dtype=torch.float64).to(self.device)
+        P = L.device_f64(prices, self.device)
         if P.dim() != 2 or P.shape[0] < 1:
             raise ValueError(f"sweep takes prices [G][n], not {list(P.shape)}")
         P = P.contiguous()
@@ -328,14 +323,11 @@ class DeviceAggregator:
             rb.step(t, noise=noise_fn(t) if noise_fn else None, hist=None)
             out[:, s].copy_(rb.aggregate_groups())
             if hasattr(rb, "int_path"):
-                p = rb.int_path.view(G, rb.int_path.numel() // G)
-                counts += torch.stack([((p & L.PATH_APPROX_MASK) != 0).sum(1), ((p & L.PATH_STEPS) != 0).sum(1),
-                                       ((p & L.PATH_SECOND) != 0).sum(1)])
+                counts += L.path_counts(rb.int_path.view(G, -1), 1)
         if self.world > 1:
             torch.distributed.all_reduce(out, group=self.group)
             torch.distributed.all_reduce(counts, group=self.group)
-        a, s_, m = counts.cpu().tolist()
-        self.sweep_counts = {"approx_solves": a, "step_dp_solves": s_, "later_launch_solves": m}
+        self.sweep_counts = dict(zip(L.PATH_COUNT_KEYS, counts.cpu().tolist()))
         return out
 
     # ------------------------------------------------------------------ checkpoint / resume

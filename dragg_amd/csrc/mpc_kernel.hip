@@ -1252,7 +1252,8 @@ struct KArgs {
     dragg_mpc_dims d;
     dragg_mpc_problem p;
     // the inputs of the entry point's own, never both: explicit per-home inputs (PM_EXPLICIT kernels) or the
-    // groups' own seeds, start indices and clocks, each [G] or NULL: the shared value (PM_EPISODES kernels).
+    // groups' own seeds, start indices and clocks, each [G] or NULL: the shared value (PM_GROUPED kernels; all
+    // NULL, as KArgs{} leaves them: a grouped dragg_mpc_step).
     // One slot for both keeps the kernels' argument block, and with it the code of every other kernel, as it was
     union {
         dragg_mpc_explicit ex;
@@ -1302,21 +1303,22 @@ DEV void lag_finish(const KArgs& a, int home) {
 // PM, the prologue's mode (a template argument of every solve kernel; the host picks the instantiation, so
 // the kernels of an ordinary step carry no trace of the grouped indexing): the step's inputs from the
 // problem arrays, explicit per-home inputs (dragg_mpc_solve_explicit), or a step of a grouped batch
-// (PM_GROUPED), or a step of a batch of episodes (PM_EPISODES, dragg_mpc_step_episodes: a grouped batch whose
-// groups each have their own noise seed, start index and clock)
-constexpr int PM_STEP = 0, PM_EXPLICIT = 1, PM_GROUPED = 2, PM_EPISODES = 3;
+// (PM_GROUPED: dragg_mpc_step with dims.n_groups > 1 and dragg_mpc_step_episodes, whose groups may each
+// have their own noise seed, start index and clock)
+constexpr int PM_STEP = 0, PM_EXPLICIT = 1, PM_GROUPED = 2;
 
-// PM_EPISODES: the group of a home and the three values of its own.  The group is the same for the whole
-// block (taken from the first lane's home), so the loads are scalar
-struct Episode {
+// PM_GROUPED: the group of a home (G consecutive replicas of N / G base homes), its base home and the three
+// values of the group's own, each the shared one where a.ep's member is NULL.  The group is the same for the
+// whole block (taken from the first lane's home), so the loads are scalar
+struct Group {
     unsigned g, base;      // the home's group and its base home
     int t, start;          // the group's timestep (< 0: idle) and start index
     uint64_t seed;
 };
-DEV Episode episode_of(const KArgs& a, int home) {
+DEV Group group_of(const KArgs& a, int home) {
     const unsigned hs = (unsigned)__builtin_amdgcn_readfirstlane(home);
     const unsigned nb = (unsigned)a.d.n_homes / (unsigned)max(a.d.n_groups, 1);
-    Episode e;
+    Group e;
     e.g = hs / nb;
     e.base = hs - e.g * nb;
     e.t = a.ep.timestep ? a.ep.timestep[e.g] : a.t;
@@ -1327,7 +1329,7 @@ DEV Episode episode_of(const KArgs& a, int home) {
 // An idle group takes no part in the step: its clock is negative, or its window [start + t, start + t + H]
 // does not lie inside the environment lists (the host cannot see the device-resident clocks: the kernel
 // must not read past the lists)
-DEV bool episode_idle(const KArgs& a, const Episode& e) {
+DEV bool group_idle(const KArgs& a, const Group& e) {
     return e.t < 0 || e.start < 0 || (long long)e.start + e.t + a.d.horizon >= (long long)a.d.n_env;
 }
 
@@ -1357,31 +1359,24 @@ DEV int prologue(const KArgs& a, Home& h, const Lds& L, const Io& io, int lane, 
         __syncthreads();
     } else {
 #pragma clang fp contract(off)   // draw sizes, Tw0 mixing and the season test as in numpy
-        // (a batch of episodes: the group's own clock, start index and seed in place of the shared ones)
-        Episode ep{};
-        if (PM == PM_EPISODES) ep = episode_of(a, home);
-        const int t = PM == PM_EPISODES ? ep.t : a.t;
+        // (a grouped batch: the group's own clock, start index and seed in place of the shared ones)
+        Group grp{};
+        if (PM == PM_GROUPED) grp = group_of(a, home);
+        const int t = PM == PM_GROUPED ? grp.t : a.t;
         h.t = t;
         const int dt = h.dt;
         const int lag = H / dt + 1;                           // mpc_calc.py:194
         const int nraw = lag * dt;
         const int base_hour = t / dt;
-        const int s0 = (PM == PM_EPISODES ? ep.start : a.p.start_index) + t;
-        // a grouped batch (dims.n_groups = G > 1: G consecutive replicas of N / G base homes): the home
+        const int s0 = (PM == PM_GROUPED ? grp.start : a.p.start_index) + t;
+        // a grouped batch (dims.n_groups = G: G consecutive replicas of N / G base homes): the home
         // reads its group's price row and draws its base home's noise.  Both are the same for the whole
-        // block: computed from the first lane's home so that they stay in scalar registers
+        // block (group_of), so they stay in scalar registers
         const double* rpl = a.p.reward_price;
         int nhome = home;
         if (PM == PM_GROUPED) {
-            const unsigned hs = (unsigned)__builtin_amdgcn_readfirstlane(home);
-            const unsigned nb = (unsigned)N / (unsigned)a.d.n_groups;
-            const unsigned g = hs / nb;
-            rpl += (size_t)g * a.d.n_rp;
-            nhome = (int)(hs - g * nb);
-        }
-        if (PM == PM_EPISODES) {
-            rpl += (size_t)ep.g * a.d.n_rp;
-            nhome = (int)ep.base;
+            rpl += (size_t)grp.g * a.d.n_rp;
+            nhome = (int)grp.base;
         }
         auto rawv = [&](int idx) -> double {                  // np.repeat(list, dt) / dt
             const int hh = base_hour + idx / dt - lag;
@@ -1406,7 +1401,7 @@ DEV int prologue(const KArgs& a, Home& h, const Lds& L, const Io& io, int lane, 
             if (a.noise) z = a.noise[(size_t)k * N + home];
             else {
                 double z0, z1;
-                normal_pair(PM == PM_EPISODES ? ep.seed : a.p.seed, a.p.home_offset + nhome * max(a.p.home_stride, 1), t, k >> 1, &z0, &z1);
+                normal_pair(PM == PM_GROUPED ? grp.seed : a.p.seed, a.p.home_offset + nhome * max(a.p.home_stride, 1), t, k >> 1, &z0, &z1);
                 z = (k & 1) ? z1 : z0;
             }
             mx = fmax(mx, a.p.oat[s0 + k + 1] + pow(1.1, (double)k) * z);
@@ -1471,8 +1466,8 @@ __global__ __launch_bounds__(64) void mpc_home_kernel(KArgs a) {
     const int lane = threadIdx.x;
     const int N = a.d.n_homes;
     if (home >= N) return;
-    if constexpr (PM == PM_EPISODES)            // an idle group's blocks leave before any write
-        if (episode_idle(a, episode_of(a, home))) return;
+    if constexpr (PM == PM_GROUPED)             // an idle group's blocks leave before any write
+        if (group_idle(a, group_of(a, home))) return;
     Home h;
     const int H = a.d.horizon;
     Lds L = carve(smem, H);
@@ -4847,8 +4842,8 @@ __global__ __launch_bounds__(WAVE * NW, MODE == DM_FRONT ? (ILP > 1 ? 2 : 3) : M
         if (home >= N) return;
         // an idle group's blocks leave before any write; every later launch works off the lists this one
         // fills, so none of them sees an idle home
-        if constexpr (PM == PM_EPISODES)
-            if (episode_idle(a, episode_of(a, home))) return;
+        if constexpr (PM == PM_GROUPED)
+            if (group_idle(a, group_of(a, home))) return;
         if (a.clk) {
             // lag mode, main pass: a home whose previous step is not complete yet goes to the side pass
             if (threadIdx.x == 0) take = __hip_atomic_load(a.clk + home, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -5051,31 +5046,20 @@ __global__ __launch_bounds__(REP_NT) void replicate_kernel(RepSeg a, RepSeg b, i
     }
 }
 
-// (nb: the base homes of a grouped batch, N otherwise: a replica draws its base home's stream)
-__global__ void noise_kernel(int N, int H, uint64_t seed, int off, int stride, int t, double* out, int nb) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int pairs = (H + 1) / 2;
-    if (idx >= N * pairs) return;
-    const int home = idx % N, pr = idx / N;
-    double z0, z1;
-    normal_pair(seed, off + (home % nb) * stride, t, pr, &z0, &z1);
-    out[(size_t)(2 * pr) * N + home] = z0;
-    if (2 * pr + 1 < H) out[(size_t)(2 * pr + 1) * N + home] = z1;
-}
-
-// (a batch of episodes: home r of group g = r / nb draws the stream of (seed[g], its base home, timestep[g] --
-// NULL: t); the rows of a group whose timestep is negative are left as they are)
-__global__ void noise_episodes_kernel(int N, int H, dragg_mpc_episodes ep, int off, int stride, int t, double* out,
-                                      int nb) {
+// (nb: the base homes of a grouped batch, N otherwise.  Home r of group g = r / nb draws the stream of
+// (ep.seed[g] -- NULL: seed --, its base home, ep.timestep[g] -- NULL: t); the columns of a group whose own
+// timestep is negative are left as they are)
+__global__ void noise_kernel(int N, int H, dragg_mpc_episodes ep, uint64_t seed, int off, int stride, int t,
+                             double* out, int nb) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int pairs = (H + 1) / 2;
     if (idx >= N * pairs) return;
     const int home = idx % N, pr = idx / N;
     const int g = home / nb;
     const int tg = ep.timestep ? ep.timestep[g] : t;
-    if (tg < 0) return;
+    if (ep.timestep && tg < 0) return;
     double z0, z1;
-    normal_pair(ep.seed[g], off + (home - g * nb) * stride, tg, pr, &z0, &z1);
+    normal_pair(ep.seed ? ep.seed[g] : seed, off + (home - g * nb) * stride, tg, pr, &z0, &z1);
     out[(size_t)(2 * pr) * N + home] = z0;
     if (2 * pr + 1 < H) out[(size_t)(2 * pr + 1) * N + home] = z1;
 }
@@ -5101,12 +5085,18 @@ size_t kernel_lds_bytes(const dragg_mpc_dims* d) {
     return direct_mode(d) ? (size_t)front_layout(d->horizon).bytes : (size_t)lds_doubles(d->horizon) * 8;
 }
 
+// G, the groups of these dims (n_groups 0 or 1: one), or DRAGG_E_ARG where the homes do not divide into them
+int group_count(const dragg_mpc_dims* d) {
+    const int G = max(d->n_groups, 1);
+    return d->n_groups < 0 || d->n_homes % G != 0 ? DRAGG_E_ARG : G;
+}
+
 int check_dims(const dragg_mpc_dims* d) {
     if (!d || d->n_homes < 0 || d->horizon < 1 || d->sub_steps < 1 || d->dt < 1) return DRAGG_E_ARG;
     if (d->n_homes > HOME_MASK) return DRAGG_E_ARG;                   // the deferred lists' home field
     if (d->int_mode < DRAGG_INT_ROUND || d->int_mode > DRAGG_INT_FAIL) return DRAGG_E_ARG;
     if (d->flags & ~DRAGG_FLAG_EXACT) return DRAGG_E_ARG;
-    if (d->n_groups < 0 || (d->n_groups > 1 && d->n_homes % d->n_groups != 0)) return DRAGG_E_ARG;
+    if (group_count(d) < 0) return DRAGG_E_ARG;
     if (direct_mode(d) && d->sub_steps > 15) return DRAGG_E_ARG;     // 4-bit duty in the DP record
     if (direct_mode(d) && !direct_fits(d->horizon)) return DRAGG_E_HORIZON;
     if (kernel_lds_bytes(d) > LDS_DYN_MAX) return DRAGG_E_HORIZON;
@@ -5173,7 +5163,8 @@ int hot_ilp(int dev, int N) {
 
 // The launches of a step, each described once: its kernel (the PM instantiation), its threads per block and
 // its dynamic LDS bytes, from the dims and the knobs.  The serial step, both lag passes, mid_slots and
-// dragg_mpc_kernel_info_get all read them here.
+// dragg_mpc_kernel_info_get all read them here.  Three instantiations: PM_STEP (an ordinary step, lag mode),
+// PM_EXPLICIT, and PM_GROUPED for every grouped batch (a price sweep and a batch of episodes alike).
 struct Launch { const void* kern; int nt; size_t lds; };
 struct Launches {
     Launch home;          // relax / round_lp: the whole solve, one workgroup per home
@@ -5426,18 +5417,19 @@ int dragg_mpc_step(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, dr
     const int rc = solve_args(dims, prob, hash, out, timestep, true, &a);
     if (rc || dims->n_homes == 0) return rc;
     a.noise = noise;
-    // (a grouped batch runs the kernels instantiated with the grouped prologue: an ordinary step's are untouched)
+    // (a grouped batch runs the kernels instantiated with the grouped prologue: an ordinary step's are untouched.
+    // It is dragg_mpc_step_episodes' launch with every member NULL, which is how KArgs{} left a.ep)
     return a.d.n_groups > 1 ? launch<PM_GROUPED>(a, (hipStream_t)stream) : launch<PM_STEP>(a, (hipStream_t)stream);
 }
 
-// A step of a batch of episodes: dragg_mpc_step's launches with the PM_EPISODES kernels.  The shared
+// A step of a batch of episodes: dragg_mpc_step's launches with the PM_GROUPED kernels, for any G.  The shared
 // start_index and timestep are checked against the environment lists only where a group can read them (their
-// member array is NULL); the groups' own values live on the device and are checked there (episode_idle)
+// member array is NULL); the groups' own values live on the device and are checked there (group_idle).
+// (n_homes % G: check_dims, which returns DRAGG_E_ARG for it before any other code)
 int dragg_mpc_step_episodes(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, const dragg_mpc_episodes* ep,
                             dragg_mpc_hash* hash, dragg_mpc_out* out, int32_t timestep, const double* noise,
                             void* stream) {
     if (!ep || !prob) return DRAGG_E_ARG;
-    if (dims && dims->n_homes >= 0 && dims->n_homes % max(dims->n_groups, 1) != 0) return DRAGG_E_ARG;
     dragg_mpc_problem p = *prob;
     if (ep->start_index) p.start_index = 0;
     KArgs a;
@@ -5447,7 +5439,7 @@ int dragg_mpc_step_episodes(const dragg_mpc_dims* dims, const dragg_mpc_problem*
     a.t = timestep;
     a.noise = noise;
     a.ep = *ep;
-    return launch<PM_EPISODES>(a, (hipStream_t)stream);
+    return launch<PM_GROUPED>(a, (hipStream_t)stream);
 }
 
 // one pass of a lag-mode step: solve_args, then what only lag mode needs
@@ -5554,39 +5546,39 @@ int dragg_mpc_aggregate(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, 
     return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
 }
 
-int dragg_mpc_season_noise(const dragg_mpc_dims* dims, uint64_t seed, int32_t home_offset, int32_t home_stride,
-                           int32_t timestep, double* noise_out, void* stream) {
+// the keyed draw of both noise entries.  shared_seed NULL: there is none (no problem struct at the episodes
+// entry), ep.seed must be given, and a negative shared timestep makes every group idle as in the step
+static int season_noise(const dragg_mpc_dims* dims, const dragg_mpc_episodes& ep, const uint64_t* shared_seed,
+                        int32_t home_offset, int32_t home_stride, int32_t timestep, double* noise_out, void* stream) {
     if (!dims || dims->n_homes < 0 || dims->horizon < 1) return DRAGG_E_ARG;
-    if (dims->n_groups < 0 || (dims->n_groups > 1 && dims->n_homes % dims->n_groups != 0)) return DRAGG_E_ARG;
+    const int G = group_count(dims);
+    if (G < 0) return DRAGG_E_ARG;
     const int total = dims->n_homes * ((dims->horizon + 1) / 2);
     if (total == 0) return DRAGG_OK;
-    if (!noise_out) return DRAGG_E_ARG;
-    hipLaunchKernelGGL(noise_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                       dims->n_homes, dims->horizon, seed, home_offset, max(home_stride, 1), timestep, noise_out,
-                       dims->n_homes / max(dims->n_groups, 1));
+    if (!noise_out || (!shared_seed && !ep.seed)) return DRAGG_E_ARG;
+    if (!shared_seed && !ep.timestep && timestep < 0) return DRAGG_OK;
+    hipLaunchKernelGGL(noise_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, dims->n_homes,
+                       dims->horizon, ep, shared_seed ? *shared_seed : 0, home_offset, max(home_stride, 1), timestep,
+                       noise_out, dims->n_homes / G);
     return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+}
+
+int dragg_mpc_season_noise(const dragg_mpc_dims* dims, uint64_t seed, int32_t home_offset, int32_t home_stride,
+                           int32_t timestep, double* noise_out, void* stream) {
+    return season_noise(dims, dragg_mpc_episodes{}, &seed, home_offset, home_stride, timestep, noise_out, stream);
 }
 
 int dragg_mpc_season_noise_episodes(const dragg_mpc_dims* dims, const dragg_mpc_episodes* ep, int32_t home_offset,
                                     int32_t home_stride, int32_t timestep, double* noise_out, void* stream) {
-    if (!dims || dims->n_homes < 0 || dims->horizon < 1 || dims->n_groups < 0 || !ep) return DRAGG_E_ARG;
-    const int G = max(dims->n_groups, 1);
-    if (dims->n_homes % G != 0) return DRAGG_E_ARG;
-    const int total = dims->n_homes * ((dims->horizon + 1) / 2);
-    if (total == 0) return DRAGG_OK;
-    if (!noise_out || !ep->seed) return DRAGG_E_ARG;           // (no problem struct here: no shared seed)
-    hipLaunchKernelGGL(noise_episodes_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                       dims->n_homes, dims->horizon, *ep, home_offset, max(home_stride, 1), timestep, noise_out,
-                       dims->n_homes / G);
-    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+    if (!ep) return DRAGG_E_ARG;
+    return season_noise(dims, *ep, nullptr, home_offset, home_stride, timestep, noise_out, stream);
 }
 
 int dragg_mpc_replicate(const dragg_mpc_dims* dims, const dragg_mpc_hash* src_hash, dragg_mpc_hash* dst_hash,
                         void* stream) {
-    if (!dims || dims->n_homes < 0 || dims->horizon < 1 || dims->n_groups < 0 || !src_hash || !dst_hash)
-        return DRAGG_E_ARG;
-    const int G = max(dims->n_groups, 1);
-    if (dims->n_homes % G != 0) return DRAGG_E_ARG;
+    if (!dims || dims->n_homes < 0 || dims->horizon < 1 || !src_hash || !dst_hash) return DRAGG_E_ARG;
+    const int G = group_count(dims);
+    if (G < 0) return DRAGG_E_ARG;
     if (dims->n_homes == 0) return DRAGG_OK;
     if (!src_hash->vals || !src_hash->fc || !dst_hash->vals || !dst_hash->fc) return DRAGG_E_ARG;
     const long long Nb = dims->n_homes / G;
@@ -5604,10 +5596,9 @@ int dragg_mpc_replicate(const dragg_mpc_dims* dims, const dragg_mpc_hash* src_ha
 
 int dragg_mpc_aggregate_groups(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, double* out, void* stream) {
     // n_homes == 0: every group's sums are zero (vals may be NULL)
-    if (!dims || !hash || (!hash->vals && dims->n_homes > 0) || !out || dims->n_homes < 0 || dims->n_groups < 0)
-        return DRAGG_E_ARG;
-    const int G = max(dims->n_groups, 1);
-    if (dims->n_homes % G != 0) return DRAGG_E_ARG;
+    if (!dims || !hash || (!hash->vals && dims->n_homes > 0) || !out || dims->n_homes < 0) return DRAGG_E_ARG;
+    const int G = group_count(dims);
+    if (G < 0) return DRAGG_E_ARG;
     hipLaunchKernelGGL(aggregate_groups_kernel, dim3(G), dim3(AGG_NT), 0, (hipStream_t)stream, hash->vals,
                        dims->n_homes, dims->n_homes / G, out);
     return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;

@@ -187,9 +187,7 @@ class MPCBatch:
         takes [G][n], one list per group (every row n entries), or one list for every group."""
         G = getattr(self, "groups", 1)
         if G > 1:
-            if not torch.is_tensor(rp):
-                rp = torch.as_tensor(np.asarray(rp, dtype=float), dtype=torch.float64)
-            rp = rp.detach().to(device=self.device, dtype=torch.float64)
+            rp = L.device_f64(rp, self.device)
             if rp.dim() < 2:
                 rp = rp.reshape(1, -1).expand(G, -1)
             if rp.dim() != 2 or rp.shape[0] != G:

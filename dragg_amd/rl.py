@@ -22,6 +22,8 @@ setpoint (`gen_setpoint`, aggregator.py:677-696), clipped to `rl.utility.action_
 """
 import numpy as np
 
+from ._lib import episode_mask
+
 
 def setpoint_update(state, timestep, agg_load, max_poss_load, prev_timesteps):
     """`Aggregator.gen_setpoint`'s rule (aggregator.py:677-696), once, for the runner and for every
@@ -145,14 +147,7 @@ class VectorEnv:
         self._sp = [None] * self.E
 
     def _host_mask(self, mask):
-        if mask is None:
-            return np.ones(self.E, dtype=bool)
-        a = np.asarray(mask.cpu() if hasattr(mask, "cpu") else mask)
-        if a.dtype != bool:
-            m = np.zeros(self.E, dtype=bool)
-            m[a.reshape(-1).astype(np.int64)] = True
-            a = m
-        return a
+        return np.asarray(episode_mask(mask.cpu() if hasattr(mask, "cpu") else mask, self.E))
 
     def _setpoint(self, e):
         st = setpoint_update(self._sp[e], int(self.timestep[e]), float(self.agg_load[e]), self.max_poss_load,

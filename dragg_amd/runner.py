@@ -111,13 +111,18 @@ class Aggregator:
                 R.write_home_configs(self.outputs_dir, self.all_homes, n)
         self.max_poss_load = sum(I.max_load(h) for h in self.all_homes)
 
+    def _checked_community(self):
+        """What either device aggregator is built from: the checked homes (aggregator.py:762-765), OAT, GHI, tou."""
+        checked = [h for h in self.all_homes if self.check_type == "all" or h["type"] == self.check_type]
+        col = lambda c: self.all_data[c].to_numpy(dtype=float)  # noqa: E731
+        return checked, col("OAT"), col("GHI"), col("tou")
+
     def _device_community(self):
         """The checked homes (aggregator.py:762-765 / 879-882) as this rank's device shard."""
         from .aggregator import DeviceAggregator
-        self.checked = [h for h in self.all_homes if self.check_type == "all" or h["type"] == self.check_type]
+        self.checked, oat, ghi, tou = self._checked_community()
         self._hist_rows = 0                 # steps of the history already on rank 0 (_history)
-        col = lambda c: self.all_data[c].to_numpy(dtype=float)  # noqa: E731
-        self.dev = DeviceAggregator(self.checked, col("OAT"), col("GHI"), col("tou"), self.start_hour_index,
+        self.dev = DeviceAggregator(self.checked, oat, ghi, tou, self.start_hour_index,
                                     self.num_timesteps, reward_price=self.reward_price, int_mode=self.int_mode,
                                     seed=int(self.config["simulation"]["random_seed"]), rank=self.rank,
                                     world=self.world, group=self.group, device=self.device,
@@ -220,9 +225,8 @@ class Aggregator:
             self.flush()
         E = int(episodes)
         seed = int(self.config["simulation"]["random_seed"])
-        checked = [h for h in self.all_homes if self.check_type == "all" or h["type"] == self.check_type]
-        col = lambda c: self.all_data[c].to_numpy(dtype=float)  # noqa: E731
-        va = VectorAggregator(checked, col("OAT"), col("GHI"), col("tou"), E,
+        checked, oat, ghi, tou = self._checked_community()
+        va = VectorAggregator(checked, oat, ghi, tou, E,
                               [seed + e for e in range(E)] if seeds is None else seeds,
                               [self.start_hour_index] * E if start_indices is None else start_indices,
                               self.num_timesteps, int_mode=self.int_mode, device=self.device,

@@ -62,21 +62,7 @@ class VectorAggregator:
     # ------------------------------------------------------------------ masks and keys
     def _mask(self, mask):
         """None (every episode), a bool sequence / tensor [E], or episode indices -> device bool [E]."""
-        if mask is None:
-            return torch.ones(self.E, dtype=torch.bool, device=self.device)
-        if torch.is_tensor(mask) and mask.dtype == torch.bool:
-            m = mask.to(self.device)
-        else:
-            a = np.asarray(mask.cpu() if torch.is_tensor(mask) else mask)
-            if a.dtype == bool:
-                m = torch.as_tensor(a, device=self.device)
-            else:
-                m = torch.zeros(self.E, dtype=torch.bool)
-                m[torch.as_tensor(a.reshape(-1).astype(np.int64))] = True
-                m = m.to(self.device)
-        if tuple(m.shape) != (self.E,):
-            raise ValueError(f"a mask of {self.E} episodes, not {list(m.shape)}")
-        return m
+        return torch.as_tensor(L.episode_mask(mask, self.E), device=self.device)
 
     def check_start(self, start):
         """The last step of an episode from `start` must read inside the environment lists
@@ -161,8 +147,7 @@ class VectorAggregator:
         episode e's reward-price list); the others stay idle.  -> device tensor [E][3], collect_data's
         [agg_load, forecast_load, agg_cost] per episode (an idle episode's row: its state's, i.e. its last
         step's sums, NaN before its first).  The active clocks advance on the device."""
-        P = torch.as_tensor(np.asarray(prices, dtype=float) if not torch.is_tensor(prices) else prices,
-                            dtype=torch.float64).to(self.device)
+        P = L.device_f64(prices, self.device)
         if P.dim() == 1:
             P = P.reshape(-1, 1)
         if P.dim() != 2 or P.shape[0] != self.E:
@@ -220,9 +205,7 @@ class VectorAggregator:
         """Per episode, the solves so far by int_path (the masks of DeviceAggregator.approx_counts):
         {"approx_solves": [E], "step_dp_solves": [E], "later_launch_solves": [E]}."""
         p = self.path_hist.view(self.num_timesteps, self.E, self.Nb)        # (cleared rows are 0)
-        v = torch.stack([((p & L.PATH_APPROX_MASK) != 0).sum((0, 2)), ((p & L.PATH_STEPS) != 0).sum((0, 2)),
-                         ((p & L.PATH_SECOND) != 0).sum((0, 2))]).cpu().tolist()
-        return {"approx_solves": v[0], "step_dp_solves": v[1], "later_launch_solves": v[2]}
+        return dict(zip(L.PATH_COUNT_KEYS, L.path_counts(p, (0, 2)).cpu().tolist()))
 
     def status_counts(self):
         """Solves so far by dragg_status over every episode: {status name: count}."""

@@ -144,7 +144,9 @@ typedef struct dragg_mpc_dims {
                               (params, home_type, draw_hourly, vals, fc, the outputs, an
                               explicit noise array) is n_homes wide as always: the caller
                               tiles the base community's G times (state: dragg_mpc_replicate).
-                              dragg_mpc_step only: dragg_mpc_solve_explicit and the lag-mode
+                              Such a step is dragg_mpc_step_episodes' (below) with every group
+                              on the shared seed, start index and clock: one mechanism, one
+                              set of kernels.  dragg_mpc_solve_explicit and the lag-mode
                               entry points return DRAGG_E_ARG for G > 1                    */
 } dragg_mpc_dims;
 
@@ -328,9 +330,11 @@ int dragg_mpc_replicate(const dragg_mpc_dims* dims, const dragg_mpc_hash* src_ha
 int dragg_mpc_aggregate_groups(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, double* out,
                                void* stream);
 
-/* Vectorised episodes: a grouped batch (dims.n_groups = G, G >= 1 here) whose every group is a full episode
-   of the base community, with its own season-noise seed, its own start index into the environment lists
-   and its own clock.  Home r is in group g = r / Nb and has base home b = r % Nb; its step is exactly
+/* Vectorised episodes: the grouped batch of dims.n_groups (G >= 1 here) with up to three values of each
+   group's own, so that every group is a full episode of the base community: its own season-noise seed, its
+   own start index into the environment lists and its own clock.  This is the one grouped step:
+   dragg_mpc_step with G > 1 runs it with all three shared.  Home r is in group g = r / Nb and has base
+   home b = r % Nb; its step is exactly
    dragg_mpc_step of base home b with seed ep.seed[g] (global home home_offset + b * home_stride),
    start_index ep.start_index[g], timestep ep.timestep[g] and reward-price row g -- nothing else changes, so
    group g equals, bit for bit, a plain batch of the Nb base homes run with those values.  The clock is per
@@ -355,7 +359,8 @@ int dragg_mpc_step_episodes(const dragg_mpc_dims* dims, const dragg_mpc_problem*
                             const dragg_mpc_episodes* ep, dragg_mpc_hash* hash, dragg_mpc_out* out,
                             int32_t timestep, const double* noise, void* stream);
 
-/* The keyed season-noise stream of a batch of episodes: writes [H][N] normals, home r drawing the stream of
+/* The keyed season-noise stream of a batch of episodes (dragg_mpc_season_noise's draw, the same kernel, with
+   the groups' own seeds and clocks): writes [H][N] normals, home r drawing the stream of
    (ep.seed[g], global home home_offset + (r % Nb) * home_stride, ep.timestep[g]) -- ep.timestep NULL: the
    `timestep` argument; ep.seed must be given (there is no shared seed here); ep.start_index is not read.  The
    columns of an idle group (timestep < 0) are left as they are. */

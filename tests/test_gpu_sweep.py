@@ -127,6 +127,29 @@ def test_replica_homes_equal_base_homes(gpu, community):
         assert counts["later_launch_solves"][g] == int(((path & L.PATH_SECOND) != 0).sum())
 
 
+def test_grouped_step_is_the_episodes_step(gpu, community):
+    """A grouped dragg_mpc_step is dragg_mpc_step_episodes with every member NULL: from the same replicated
+    state and under the same price rows, both entry points leave the same bits."""
+    from dragg_amd.mpc import MPCBatch
+    homes, (oat, ghi, tou) = community
+    agg = _agg(community)
+    t = agg.timestep
+    got = []
+    for episodes in (False, True):
+        rb = MPCBatch(homes, oat, ghi, tou, 0, [0.0], seed=5, groups=3)
+        rb.set_reward_price(_prices())
+        rb.replicate_from(agg.batch)
+        if episodes:
+            rb.step_episodes(None, None, None, t=t)
+        else:
+            rb.step(t)
+        got.append((_bits(rb.vals).clone(), _bits(rb.fc_store).clone(), rb.status.clone(), _bits(rb.obj).clone(),
+                    rb.int_path.clone()))
+    assert (got[0][2] == 0).any() and not torch.equal(got[0][0], _bits(agg.batch.vals).repeat(1, 3))   # (it stepped)
+    for name, a, b in zip(("vals", "fc_store", "status", "obj", "int_path"), *got):
+        assert torch.equal(a, b), name
+
+
 # ------------------------------------------------------------------ dragg_mpc_replicate
 def _replicate_raw(L, lib, src_vals, src_fc, G, H):
     """dragg_mpc_replicate on raw int64 bit patterns ([NVAL][Nb], [Nb][NFC][H]) -> the replicas' arrays."""
@@ -235,6 +258,14 @@ def test_grouped_season_noise_is_the_base_homes(gpu, off, stride):
     for g in range(G):
         assert torch.equal(grouped[:, g * Nb:(g + 1) * Nb], base), g
     assert not torch.equal(noise(G * Nb, 0)[:, Nb:2 * Nb], base)       # (ungrouped: 15 homes of their own)
+    # the episodes entry with every group on that seed and the shared timestep: the same draw (one kernel)
+    seeds = torch.full((G,), 11, dtype=torch.int64, device=gpu)
+    ep = L.Episodes(seed=L.ptr(seeds), start_index=None, timestep=None)
+    dims = L.Dims(n_homes=G * Nb, horizon=H, sub_steps=6, dt=4, n_groups=G)
+    out = torch.zeros((H, G * Nb), dtype=torch.float64, device=gpu)
+    L.check(lib.dragg_mpc_season_noise_episodes(ctypes.byref(dims), ctypes.byref(ep), off, stride, 4, L.ptr(out),
+                                                L.stream_ptr()))
+    assert torch.equal(_bits(out), _bits(grouped))
 
 
 # ------------------------------------------------------------------ other modes

@@ -350,3 +350,61 @@ def test_runner_rl_vector_builds_the_environment(tmp_path):
     a.world = 2
     with pytest.raises(ValueError, match="one rank"):
         a.rl_vector(2)
+
+
+# ------------------------------------------------------------------ the helpers both grouped-batch consumers share
+def test_path_counts_equal_the_written_out_sums():
+    rng = np.random.default_rng(4)
+    bits = np.array([0, 1, 0x800, L.PATH_SECOND, L.PATH_STEPS, L.PATH_SECOND | L.PATH_STEPS, L.PATH_SECOND | 3,
+                     L.PATH_FAIL_T], dtype=np.int32)
+    a = bits[rng.integers(0, len(bits), size=(4, 3, 5))]                    # [T][G][Nb]
+    assert all((a == b).any() for b in bits)
+    p = torch.as_tensor(a)
+    masks = (L.PATH_APPROX_MASK, L.PATH_STEPS, L.PATH_SECOND)
+    assert L.PATH_COUNT_KEYS == ("approx_solves", "step_dp_solves", "later_launch_solves")
+    total = L.path_counts(p)
+    assert total.dtype == torch.int64 and total.tolist() == [int(((a & m) != 0).sum()) for m in masks]
+    per_group = L.path_counts(p, (0, 2))                                    # VectorAggregator.approx_counts
+    assert per_group.tolist() == [((a & m) != 0).sum((0, 2)).tolist() for m in masks]
+    one_step = L.path_counts(p[1].reshape(3, -1), 1)                        # DeviceAggregator.sweep, per step
+    assert one_step.tolist() == [((a[1] & m) != 0).sum(1).tolist() for m in masks]
+    assert per_group.sum(1).tolist() == total.tolist() and 0 < total[0] < a.size
+
+
+def test_episode_mask_none_bool_indices_and_wrong_length():
+    E = 4
+    assert L.episode_mask(None, E).tolist() == [True] * 4
+    want = [False, True, False, True]
+    for m in (want, np.array(want), torch.tensor(want), [1, 3], (3, 1), np.array([1, 3]), torch.tensor([3, 1]),
+              np.array([[1], [3]])):
+        got = L.episode_mask(m, E)
+        assert got.dtype in (bool, torch.bool) and tuple(got.shape) == (E,) and got.tolist() == want, m
+    assert L.episode_mask(torch.tensor(want), E).dtype == torch.bool         # (a bool tensor stays a tensor)
+    assert L.episode_mask([], E).tolist() == [False] * 4
+    for bad in ([True, False], np.ones(5, bool), torch.ones(3, dtype=torch.bool)):
+        with pytest.raises(ValueError, match="a mask of 4 episodes"):
+            L.episode_mask(bad, E)
+    with pytest.raises(IndexError):
+        L.episode_mask([4], E)
+    # both users: the device mask of VectorAggregator, the host mask of VectorEnv
+    from dragg_amd.rl import VectorEnv
+    va = _va(E, [1, 2, 3, 4], [0] * 4)
+    assert va._mask([1, 3]).tolist() == want and va._mask(torch.tensor(want)).dtype == torch.bool
+    env = VectorEnv.__new__(VectorEnv)
+    env.E = E
+    assert isinstance(env._host_mask(torch.tensor(want)), np.ndarray) and env._host_mask([3, 1]).tolist() == want
+    with pytest.raises(ValueError):
+        va._mask([True] * 3)
+
+
+def test_device_f64_from_a_list_an_array_and_a_cpu_tensor():
+    want = [[0.5, -1.25, 3.0], [2.0, 0.0, 1e-3]]
+    for x in (want, np.array(want), np.array(want, dtype=np.float32), torch.tensor(want, dtype=torch.float32),
+              torch.tensor([[1, 2, 3], [4, 5, 6]], dtype=torch.int32)):
+        t = L.device_f64(x, CPU)
+        assert t.dtype == torch.float64 and t.device == CPU and tuple(t.shape) == (2, 3)
+        ref = np.asarray(x.numpy() if torch.is_tensor(x) else x, dtype=np.float64)
+        assert np.array_equal(t.numpy(), ref)                              # (exact: every value widens exactly)
+    g = torch.tensor(want, dtype=torch.float64, requires_grad=True)
+    assert not L.device_f64(g, CPU).requires_grad
+    assert L.device_f64(3, CPU).shape == () and L.device_f64([0.25], CPU).tolist() == [0.25]
