@@ -96,30 +96,28 @@ def lag_list_ints(n):
     return n + 4
 
 
-def workspace_regions(N, H, cells=False):
-    """Byte offset of every region of the round-mode workspace, in order, and the total (mirrors
-    mpc_kernel.hip's par_region_bytes ... direct_workspace_bytes; dragg_mpc_workspace_bytes is the total,
-    dragg_mpc_side_workspace_bytes the span [deferred, w_rows)).  A list is [N] i32 entries, then its
-    length and take counter.  cells: with a reward-price list (dims.n_rp > 1)."""
-    def up(x):
-        return (x + 255) // 256 * 256
-    # mpc_kernel.hip's NB_CAP, NF_BIG, NF_MID, SECOND_SLOTS, MID_SLOTS_MAX, NARROW_SLOTS, NCELL (= CELL_STRIDE)
-    NB_CAP, NF_BIG, NF_MID, SECOND_SLOTS, MID_SLOTS, NARROW_SLOTS, NCELL = 336, 2048, 384, 512, 2048, 16, 1024
-    # step_slot_bytes(): [2][POOL_CAP = 2^20] f64, [2][MC_CAP = 8 NP_CAP = 8 x 32768] i32, [2][LW_ROWS = 256][64] (x, v)
-    step_slot = 2 * 2 ** 20 * 8 + 2 * 8 * 32768 * 4 + 2 * 256 * 64 * 16
-    list_bytes = (N + 2) * 4
-    r = {"back_pointers": 0}                           # [N][H][NB_CAP] u16
-    r["solutions"] = up(N * H * NB_CAP * 2)            # [N][8H] f64 stage-slot solutions
-    r["deferred"] = r["solutions"] + N * 8 * H * 8     # list: hot -> mid (not 256-aligned)
-    r["big_rows"] = up(r["deferred"] + list_bytes)     # [SECOND_SLOTS][H][NF_BIG] u16
-    r["steps_list"] = up(r["big_rows"] + SECOND_SLOTS * H * NF_BIG * 2)    # list: any -> step-function DP
-    r["steps_pools"] = up(r["steps_list"] + list_bytes)                    # [min(N, 16)] block slots
-    r["mid_list"] = up(r["steps_pools"] + min(N, NARROW_SLOTS) * step_slot)   # list: mid -> big
-    r["mid_rows"] = up(r["mid_list"] + list_bytes)     # [MID_SLOTS][H][NF_MID] u16
-    r["w_rows"] = up(r["mid_rows"] + MID_SLOTS * H * NF_MID * 2)           # [N][H + 1][64] (x, v)
-    r["cell_rows"] = up(r["w_rows"] + N * (H + 1) * 64 * 16)               # [N][H + 1][NCELL] u16 (cells)
-    r["total"] = r["cell_rows"] + (N * (H + 1) * NCELL * 2 if cells else 0)
-    return r
+# a work-list entry's home field (mpc_kernel.hip's HOME_MASK; bits 28-31: flags and the deferred chain)
+LIST_HOME_MASK = 0x0FFFFFFF
+WORK_LISTS = ("deferred", "steps_list", "mid_list")
+
+
+class WorkspaceRegions(ctypes.Structure):
+    """dragg_mpc_workspace_regions: byte offsets of the workspace's regions in order, then the total."""
+    _fields_ = [(f, ctypes.c_int64) for f in ("back_pointers", "solutions", "deferred", "big_rows", "steps_list",
+                                              "steps_pools", "mid_list", "mid_rows", "w_rows", "cell_rows", "total")]
+
+
+def workspace_regions(dims, H=None, cells=False):
+    """Byte offset of every region of the workspace for these dims, in order, and the total, from the library
+    (dragg_mpc_workspace_regions_get; dragg_mpc_workspace_bytes is the total, dragg_mpc_side_workspace_bytes
+    the span [deferred, w_rows)).  A list is [N] i32 entries, then its length and take counter.
+    The earlier call form (N, H, cells) still works: a round-mode batch of N homes, with a reward-price list
+    if `cells` (the layout depends on nothing else in the dims)."""
+    if H is not None:
+        dims = Dims(n_homes=dims, horizon=H, sub_steps=6, dt=1, n_rp=H if cells else 1, int_mode=INT_ROUND)
+    r = WorkspaceRegions()
+    check(load().dragg_mpc_workspace_regions_get(ctypes.byref(dims), ctypes.byref(r)))
+    return {f: getattr(r, f) for f, _ in WorkspaceRegions._fields_}
 
 
 NLAUNCH = 4                    # DRAGG_NLAUNCH: hot, big, mid, narrow (dragg_mpc_kernel_info)
@@ -132,7 +130,7 @@ class KernelInfo(ctypes.Structure):
 
 
 EXPORTS = ["dragg_mpc_abi_version", "dragg_mpc_strerror", "dragg_mpc_lds_bytes", "dragg_mpc_workspace_bytes",
-           "dragg_mpc_kernel_info_get", "dragg_mpc_step",
+           "dragg_mpc_workspace_regions_get", "dragg_mpc_kernel_info_get", "dragg_mpc_step",
            "dragg_mpc_solve_explicit", "dragg_mpc_aggregate", "dragg_mpc_season_noise", "dragg_mpc_reload_knobs",
            "dragg_mpc_lag_reset", "dragg_mpc_step_main", "dragg_mpc_step_side", "dragg_mpc_aggregate_rows",
            "dragg_mpc_side_workspace_bytes", "dragg_mpc_side_grid", "dragg_mpc_source_hash",
@@ -178,6 +176,7 @@ def load(path=LIB_PATH):
     lib.dragg_mpc_workspace_bytes.restype = ctypes.c_int64
     lib.dragg_mpc_side_workspace_bytes.argtypes = [ctypes.POINTER(Dims)]
     lib.dragg_mpc_side_workspace_bytes.restype = ctypes.c_int64
+    lib.dragg_mpc_workspace_regions_get.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(WorkspaceRegions)]
     lib.dragg_mpc_side_grid.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(ctypes.c_int32)]
     lib.dragg_mpc_source_hash.restype = ctypes.c_char_p
     lib.dragg_mpc_step.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Problem), ctypes.POINTER(Hash),

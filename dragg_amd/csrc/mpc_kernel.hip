@@ -1575,6 +1575,41 @@ __host__ __device__ inline bool direct_compact(int H) {
 }
 __host__ __device__ inline bool direct_fits(int H) { return seg_cap(H) <= NB_CAP; }
 
+// A device work list: [N] i32 entries, its length at [N], the persistent launch's take counter at [N + 1].
+// A launch pushes the homes (chains) it leaves to a later one; the later, persistent launch's blocks take them.
+constexpr int HOME_MASK = 0x0FFFFFFF;
+constexpr int BK_OK = 1 << 28;           // the bucketed DP found a schedule (in the solution rows)
+constexpr int BK_DONE = 1 << 29;         // the bucketed DP already ran for the deferred chain (mid -> big)
+constexpr int BK_BEAM = (int)(1u << 31); // ... and that schedule is the beam pass's (diagnostic: int_path bit 17)
+// step-function list entries (bit 31, the big list's BK_BEAM): a chain the hot launch handed straight over
+// (a feasible set narrower than one duty step, dp_front -2), whose bucketed DP -- the upper bound of the
+// step-function DP and its capacity escape's schedule -- the step-function launch runs itself
+constexpr int BK_NEED = (int)(1u << 31);
+// an entry: home (< 2^28) | deferred chain << 30, then the pusher ORs the BK_* flags on; unpacked, flags holds
+// bits 28, 29 and 31 (BK_BEAM in the big list, BK_NEED -- the same bit -- in the step-function list)
+struct ListEntry { int home, chain, flags; };
+__host__ __device__ inline int list_entry(int home, int chain = 0) { return home | (chain << 30); }
+__host__ __device__ inline ListEntry list_unpack(int e) { return {e & HOME_MASK, (e >> 30) & 1, e & (BK_DONE | BK_OK | BK_BEAM)}; }
+__host__ __device__ constexpr size_t list_bytes(int N) { return (size_t)(N + 2) * sizeof(int); }
+// (the public macro has allowed two spare ints past the length and the take counter since it was fixed in the ABI)
+static_assert(DRAGG_LAG_LIST_INTS(0) * sizeof(int) == list_bytes(0) + 2 * sizeof(int) &&
+              DRAGG_LAG_LIST_INTS(7) * sizeof(int) == list_bytes(7) + 2 * sizeof(int), "DRAGG_LAG_LIST_INTS: a list + 2 ints");
+struct WorkList {
+    int* e;
+    int N;
+    __device__ __forceinline__ void push(int entry) const { e[atomicAdd(e + N, 1)] = entry; }          // (one lane calls it)
+    __device__ __forceinline__ int count() const { return min(e[N], N); }
+    // the persistent take, by every thread of a block: the next entry's index through `slot` (a __shared__ int)
+    __device__ __forceinline__ int next(int& slot) const {
+        __syncthreads();
+        if (threadIdx.x == 0) slot = (int)gridDim.x + atomicAdd(e + N + 1, 1);
+        __syncthreads();
+        return slot;
+    }
+    __host__ __device__ int* tail() const { return e + N; }                      // (length, take): reset_lists
+};
+__host__ __device__ inline WorkList work_list(char* base, size_t off, int N) { return {reinterpret_cast<int*>(base + off), N}; }
+
 // Byte offsets of the direct kernel's LDS carve (one function for the device carve and the
 // host's launch size, so the two cannot disagree).
 // direct kernel workspace: [N][H][NB_CAP] u16 DP back-pointers, then [N][8H] f64 solutions
@@ -1589,7 +1624,7 @@ __host__ __device__ inline size_t par_region_bytes(int N, int H) {
 // regions (back-pointers, solutions, LP rows, cell rows) come before or after it.
 __host__ __device__ inline size_t defer_offset(int N, int H) { return par_region_bytes(N, H) + (size_t)N * 8 * H * 8; }
 __host__ __device__ inline size_t big_region_offset(int N, int H) {
-    return (defer_offset(N, H) + (size_t)(N + 2) * sizeof(int) + 255) / 256 * 256;
+    return (defer_offset(N, H) + list_bytes(N) + 255) / 256 * 256;
 }
 __host__ __device__ inline size_t big_region_bytes(int H) { return (size_t)SECOND_SLOTS * H * NF_BIG * sizeof(uint16_t); }
 // then the list of homes the second launch hands to DM_NARROW ([N] i32 + its length) and
@@ -1605,7 +1640,7 @@ __host__ __device__ inline size_t narrow_list_offset(int N, int H) {
     return (big_region_offset(N, H) + big_region_bytes(H) + 255) / 256 * 256;
 }
 __host__ __device__ inline size_t narrow_region_offset(int N, int H) {
-    return (narrow_list_offset(N, H) + (size_t)(N + 2) * sizeof(int) + 255) / 256 * 256;
+    return (narrow_list_offset(N, H) + list_bytes(N) + 255) / 256 * 256;
 }
 // then the list of homes the mid launch hands to the big one ([N] i32 + length) and (256-aligned)
 // the mid launch's back-pointer rows [MID_SLOTS_MAX][H][NF_MID] u16
@@ -1613,7 +1648,7 @@ __host__ __device__ inline size_t mid_list_offset(int N, int H) {
     return (narrow_region_offset(N, H) + (size_t)narrow_slots(N) * step_slot_bytes() + 255) / 256 * 256;
 }
 __host__ __device__ inline size_t mid_region_offset(int N, int H) {
-    return (mid_list_offset(N, H) + (size_t)(N + 2) * sizeof(int) + 255) / 256 * 256;
+    return (mid_list_offset(N, H) + list_bytes(N) + 255) / 256 * 256;
 }
 // then (256-aligned) the front DP's LP cost-to-go rows [N][H + 1][64] (x, v), per home
 __host__ __device__ inline size_t w_region_offset(int N, int H) {
@@ -4392,16 +4427,6 @@ DEV int dp_steps(const StepBufs& Sb, const double* cA, const double* cC, const d
 // bucketed DP and the big pass out of DM_FRONT keeps their registers and LDS out of the hot kernel.
 enum DirectMode { DM_FRONT = 0, DM_BUCKET = 1, DM_NARROW = 2, DM_MID = 3 };
 
-// list entries: home | BK_DONE / BK_OK | deferred chain << 30 (homes < 2^28)
-constexpr int HOME_MASK = 0x0FFFFFFF;
-constexpr int BK_OK = 1 << 28;           // the bucketed DP found a schedule (in the solution rows)
-constexpr int BK_DONE = 1 << 29;         // the bucketed DP already ran for the deferred chain (mid -> big)
-constexpr int BK_BEAM = (int)(1u << 31); // ... and that schedule is the beam pass's (diagnostic: int_path bit 17)
-// step-function list entries (bit 31, the big list's BK_BEAM): a chain the hot launch handed straight over
-// (a feasible set narrower than one duty step, dp_front -2), whose bucketed DP -- the upper bound of the
-// step-function DP and its capacity escape's schedule -- the step-function launch runs itself
-constexpr int BK_NEED = (int)(1u << 31);
-
 template <int PM, int MODE, int NW = 1, int ILP = 1>
 DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int first_chain, int eflags = 0) {
     constexpr bool SECOND = MODE == DM_BUCKET || MODE == DM_MID;   // the bucketed DP + an exact big-front pass
@@ -4412,9 +4437,9 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
     const int H = a.d.horizon;
     char* const ws = reinterpret_cast<char*>(a.p.workspace);            // per-home rows
     char* const lw = a.lws ? a.lws : ws;                                 // lists, per-block scratch
-    int* const list = reinterpret_cast<int*>(lw + defer_offset(N, H));     // [N] + length at [N]
-    int* const nlist = a.nar ? a.nar : reinterpret_cast<int*>(lw + narrow_list_offset(N, H));   // -> DM_NARROW
-    int* const blist = reinterpret_cast<int*>(lw + mid_list_offset(N, H));      // DM_MID -> DM_BUCKET
+    const WorkList list = work_list(lw, defer_offset(N, H), N);                         // hot -> DM_MID
+    const WorkList nlist{a.nar ? a.nar : reinterpret_cast<int*>(lw + narrow_list_offset(N, H)), N};   // -> DM_NARROW
+    const WorkList blist = work_list(lw, mid_list_offset(N, H), N);                        // DM_MID -> DM_BUCKET
     Home h;
     LdsD D = MODE == DM_FRONT ? carve_front(smem, H) : carve_direct(smem, H, a.d.sub_steps);
     D.par = reinterpret_cast<uint16_t*>(ws) + (size_t)home * H * NB_CAP;
@@ -4469,11 +4494,11 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
         const bool rl_prices = rl_priced(D.price, H, lane);
         const bool use_bound = rl_prices;
         if (MODE == DM_FRONT && a.force_steps) {
-            if (lane == 0) nlist[atomicAdd(nlist + N, 1)] = home;
+            if (lane == 0) nlist.push(list_entry(home));
             return;
         }
         if (MODE == DM_FRONT && rl_prices) {
-            if (lane == 0) list[atomicAdd(list + N, 1)] = home;
+            if (lane == 0) list.push(list_entry(home));
             return;
         }
         // (the second launch resumes a home at the chain the hot launch deferred: the indoor-air
@@ -4664,8 +4689,8 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
                 // which runs the bucketed DP itself (BK_NEED): one launch fewer on the chain's path (lag mode:
                 // a lagging home's side pass is hot + step-function, not hot + mid + step-function)
                 if (lane == 0) {
-                    if (r == -2 && h.S == 6) nlist[atomicAdd(nlist + N, 1)] = home | (chain << 30) | BK_NEED;
-                    else list[atomicAdd(list + N, 1)] = home | (chain << 30);
+                    if (r == -2 && h.S == 6) nlist.push(list_entry(home, chain) | BK_NEED);
+                    else list.push(list_entry(home, chain));
                 }
                 return;
             } else {
@@ -4768,8 +4793,8 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
                         // (an RL-priced chain went straight to the bucketed DP: the big launch reuses
                         // its schedule; other chains ran the regular front DP first and start over)
                         if (lane == 0)
-                            blist[atomicAdd(blist + N, 1)] = home | (chain << 30) |
-                                                             (rl_prices ? BK_DONE | (ok ? BK_OK : 0) | (beam_ub ? BK_BEAM : 0) : 0);
+                            blist.push(list_entry(home, chain) |
+                                       (rl_prices ? BK_DONE | (ok ? BK_OK : 0) | (beam_ub ? BK_BEAM : 0) : 0));
                         return;
                     }
                     if (r2 == 1) ok = true;
@@ -4787,7 +4812,7 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
                 if (MODE == DM_BUCKET && r2 == -3 && rl_prices && ok && !(a.d.flags & DRAGG_FLAG_EXACT)) {
                     int_path |= (1 << chain) | (3 << (4 + 4 * chain));
                 } else if (r2 < 0) {
-                    if (lane == 0) nlist[atomicAdd(nlist + N, 1)] = home | (chain << 30) | BK_DONE | (ok ? BK_OK : 0);
+                    if (lane == 0) nlist.push(list_entry(home, chain) | BK_DONE | (ok ? BK_OK : 0));
                     return;
                 }
             }
@@ -4850,7 +4875,7 @@ __global__ __launch_bounds__(WAVE * NW, MODE == DM_FRONT ? (ILP > 1 ? 2 : 3) : M
             __syncthreads();
             const int c = take;
             if ((c & ~LAG_SIDE) != a.t) {
-                if (threadIdx.x == 0) a.skip[atomicAdd(a.skip + N, 1)] = home;
+                if (threadIdx.x == 0) WorkList{a.skip, N}.push(list_entry(home));
                 return;
             }
             if (c & LAG_SIDE) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // the side pass's rows
@@ -4862,19 +4887,14 @@ __global__ __launch_bounds__(WAVE * NW, MODE == DM_FRONT ? (ILP > 1 ? 2 : 3) : M
     // (dynamic: a block that drew short homes takes more; measured on the RL workload: 38.2 -> 34.0
     // ms per action against a static stride), each with its own scratch rows in the workspace (slot
     // b); blocks past the list's length leave at once, every block reaches its end and exits
+    // (both passes' DM_NARROW in lag mode: the step's own list)
     const size_t lo = MODE == DM_MID ? defer_offset(N, H) : MODE == DM_BUCKET ? mid_list_offset(N, H)
                     : narrow_list_offset(N, H);
-    // (both passes' DM_NARROW in lag mode: the step's own list)
-    int* const list = (MODE == DM_NARROW && a.nar) ? a.nar : reinterpret_cast<int*>(ws + lo);
-    const int cnt = min(list[N], N);
-    for (int j = blockIdx.x; j < cnt;) {
-        const int e = list[j];                      // home | flags | deferred chain << 30
-        const int home = e & HOME_MASK, chain = (e >> 30) & 1;
-        if (home < N) solve_direct<PM, MODE, NW>(a, home, smem, blockIdx.x, chain, e & (BK_DONE | BK_OK | BK_BEAM));
-        __syncthreads();
-        if (threadIdx.x == 0) take = (int)gridDim.x + atomicAdd(list + N + 1, 1);
-        __syncthreads();
-        j = take;
+    const WorkList list{(MODE == DM_NARROW && a.nar) ? a.nar : reinterpret_cast<int*>(ws + lo), N};
+    const int cnt = list.count();
+    for (int j = blockIdx.x; j < cnt; j = list.next(take)) {
+        const ListEntry e = list_unpack(list.e[j]);
+        if (e.home < N) solve_direct<PM, MODE, NW>(a, e.home, smem, blockIdx.x, e.chain, e.flags);
     }
 }
 
@@ -4893,14 +4913,14 @@ __global__ __launch_bounds__(NT_CELL, 4) void cell_kernel(KArgs a) {
     const int tid = threadIdx.x;
     char* const ws = reinterpret_cast<char*>(a.p.workspace);
     char* const lw = a.lws ? a.lws : ws;
-    const int* const list = reinterpret_cast<const int*>(lw + defer_offset(N, H));
-    const int cnt = min(list[N], N);
+    const WorkList list = work_list(lw, defer_offset(N, H), N);
+    const int cnt = list.count();
     float* const r0 = reinterpret_cast<float*>(reinterpret_cast<char*>(smem) + (front_layout(H).bytes + 15) / 16 * 16);
     float* const r1 = r0 + CELL_ROW;
     for (int j = blockIdx.x; j < cnt; j += gridDim.x) {
-        const int e = list[j];
-        const int home = e & HOME_MASK;
-        if (home >= N || ((e >> 30) & 1) != 0) continue;        // (uniform; chain 0 entries only)
+        const ListEntry e = list_unpack(list.e[j]);
+        const int home = e.home;
+        if (home >= N || e.chain != 0) continue;                // (uniform; chain 0 entries only)
         Home h;
         LdsD D = carve_front(smem, H);
         Lds L = lp_view(D);
@@ -4941,16 +4961,12 @@ __global__ __launch_bounds__(NT_CELL, 4) void cell_kernel(KArgs a) {
 __global__ __launch_bounds__(WAVE, 2) void side_front_kernel(KArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int N = a.d.n_homes;
-    int* const list = a.hot_list;
-    const int cnt = min(list[N], N);
+    const WorkList list{a.hot_list, N};
+    const int cnt = list.count();
     __shared__ int take;
-    for (int j = blockIdx.x; j < cnt;) {
-        const int home = list[j] & HOME_MASK;
+    for (int j = blockIdx.x; j < cnt; j = list.next(take)) {
+        const int home = list_unpack(list.e[j]).home;
         if (home < N) solve_direct<PM_STEP, DM_FRONT, 1, 3>(a, home, smem, blockIdx.x, 0, 0);
-        __syncthreads();
-        if (threadIdx.x == 0) take = (int)gridDim.x + atomicAdd(list + N + 1, 1);
-        __syncthreads();
-        j = take;
     }
 }
 
@@ -5072,10 +5088,8 @@ __global__ void noise_kernel(int N, int H, dragg_mpc_episodes ep, uint64_t seed,
 // --------------------------------------------------------------------------------------
 bool direct_mode(const dragg_mpc_dims* d) { return d->int_mode == DRAGG_INT_ROUND || d->int_mode == DRAGG_INT_FAIL; }
 
+// round / fail: the whole layout (the offset chain above); round_lp: the back-pointers of its front DP alone; relax: none
 size_t workspace_bytes(const dragg_mpc_dims* d) {
-    // direct: [N][H][NB_CAP] u16 back-pointers, [N][8H] f64 solutions, the [N + 1] i32 list of
-    // deferred homes, [N][H+1][64] LP cost-to-go rows, the second launch's [SECOND_SLOTS][H][NF_BIG]
-    // u16 back-pointers; round_lp: the back-pointers of its front DP
     if (d->int_mode == DRAGG_INT_ROUND_LP) return par_region_bytes(d->n_homes, d->horizon);
     return direct_mode(d) ? direct_workspace_bytes(d->n_homes, d->horizon, d->n_rp > 1) : 0;
 }
@@ -5270,10 +5284,9 @@ int launch(const KArgs& a, hipStream_t s) {
     if (!direct_mode(&a.d)) return run(launches<PM>(a.d).home, dev, a, N, s);
     const Launches l = launches<PM>(a.d, knobs().waves, hot_ilp(dev, N));
     char* const wsb = reinterpret_cast<char*>(a.p.workspace);
-    int* const len = reinterpret_cast<int*>(wsb + defer_offset(N, H)) + N;
-    int* const nlen = reinterpret_cast<int*>(wsb + narrow_list_offset(N, H)) + N;
-    int* const blen = reinterpret_cast<int*>(wsb + mid_list_offset(N, H)) + N;
-    if (int rc = reset_lists(s, len, nlen, blen, nullptr)) return rc;
+    if (int rc = reset_lists(s, work_list(wsb, defer_offset(N, H), N).tail(), work_list(wsb, narrow_list_offset(N, H), N).tail(),
+                             work_list(wsb, mid_list_offset(N, H), N).tail(), nullptr))
+        return rc;
     if (int rc = run(l.hot, dev, a, N, s)) return rc;
     return launch_deferred(l, dev, a, min(N, CELL_BLOCKS), min(N, mid_slots<PM>(dev, l.mid)), min(N, SECOND_SLOTS),
                            min(N, NARROW_SLOTS), s);
@@ -5311,13 +5324,13 @@ int launch_lag(const KArgs& a, bool side, hipStream_t s) {
     if (int rc = current_device(&dev)) return rc;
     const int N = a.d.n_homes, H = a.d.horizon;
     const Launches l = launches<PM_STEP>(a.d, 1, hot_ilp(dev, N));
-    int* const len = reinterpret_cast<int*>(a.lws + defer_offset(N, H)) + N;
-    int* const blen = reinterpret_cast<int*>(a.lws + mid_list_offset(N, H)) + N;
+    int* const len = work_list(a.lws, defer_offset(N, H), N).tail();
+    int* const blen = work_list(a.lws, mid_list_offset(N, H), N).tail();
     // DRAGG_FORCE_STEP_DP holds here too: the hot launches list every home's chains in the step's narrow
     // list (lag->narrow), which the side pass's step-function launch then solves.  (DRAGG_WAVES_PER_HOME
     // does not: both passes run the one-wave hot kernel; the header says so.)
     if (!side) {        // (hot_list NULL and side 0, as solve_args left them)
-        if (int rc = reset_lists(s, len, blen, a.skip + N, a.nar + N)) return rc;
+        if (int rc = reset_lists(s, len, blen, WorkList{a.skip, N}.tail(), WorkList{a.nar, N}.tail())) return rc;
         if (int rc = run(l.hot, dev, a, N, s)) return rc;
         return launch_deferred(l, dev, a, min(N, CELL_BLOCKS), min(N, mid_slots<PM_STEP>(dev, l.mid)),
                                min(N, SECOND_SLOTS), 0, s);
@@ -5400,6 +5413,20 @@ int dragg_mpc_side_grid(const dragg_mpc_dims* dims, int32_t* grid4) {
     int g[4];
     side_grids(dims->n_homes, g);
     for (int i = 0; i < 4; ++i) grid4[i] = dims->n_homes > 0 ? g[i] : 0;
+    return DRAGG_OK;
+}
+
+int dragg_mpc_workspace_regions_get(const dragg_mpc_dims* dims, dragg_mpc_workspace_regions* regions) {
+    const int rc = check_dims(dims);
+    if (rc) return rc;
+    if (!regions) return DRAGG_E_ARG;
+    // (round_lp, relax: every region past the workspace's end starts at that end)
+    const int N = dims->n_homes, H = dims->horizon;
+    const size_t end = workspace_bytes(dims);
+    auto at = [end](size_t off) { return (int64_t)(off < end ? off : end); };
+    *regions = {0, at(par_region_bytes(N, H)), at(defer_offset(N, H)), at(big_region_offset(N, H)),
+                at(narrow_list_offset(N, H)), at(narrow_region_offset(N, H)), at(mid_list_offset(N, H)),
+                at(mid_region_offset(N, H)), at(w_region_offset(N, H)), at(cell_region_offset(N, H)), (int64_t)end};
     return DRAGG_OK;
 }
 

@@ -233,6 +233,26 @@ class MPCBatch:
             L.check(int(sb))
         return torch.empty(max(1, (sb + 7) // 8), dtype=torch.int64, device=self.device)
 
+    def _region(self, name, nbytes):
+        """`nbytes` of the workspace from the start of region `name` (L.workspace_regions), as uint8."""
+        off = L.workspace_regions(self.dims)[name]
+        return self.workspace.view(torch.uint8)[off:off + nbytes]
+
+    def work_list(self, name):
+        """A device work list of the last serial step ("deferred": hot -> mid, "steps_list": -> the step-function
+        DP, "mid_list": mid -> big), after a device synchronise: (its entries as int32 [min(n, N)], its length n).
+        An entry's home is `entry & L.LIST_HOME_MASK`."""
+        if name not in L.WORK_LISTS:
+            raise ValueError(f"a work list is one of {L.WORK_LISTS}, not {name!r}")
+        torch.cuda.synchronize(self.device)
+        lst = self._region(name, 4 * (self.N + 1)).view(torch.int32).cpu().numpy()
+        n = int(lst[self.N])
+        return lst[:min(n, self.N)], n
+
+    def solution_rows(self):
+        """The workspace's stage-slot solutions [N][H][8] float64 (a view; slot 7 is the diagnostics' pad)."""
+        return self._region("solutions", self.N * self.H * 64).view(torch.float64).view(self.N, self.H, 8)
+
     # ------------------------------------------------------------------ structs
     def _problem(self):
         return L.Problem(params=L.ptr(self.params), home_type=L.ptr(self.types), draw_hourly=L.ptr(self.draws),

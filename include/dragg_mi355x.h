@@ -270,6 +270,18 @@ int64_t dragg_mpc_workspace_bytes(const dragg_mpc_dims* dims);
    problem.workspace), ~0.5 GB at 10k homes, H = 48, against the workspace's 1.34 GB. */
 int64_t dragg_mpc_side_workspace_bytes(const dragg_mpc_dims* dims);
 
+/* Byte offset of every region of problem.workspace, in order, and its size (`total` =
+   dragg_mpc_workspace_bytes; the side workspace is the span [deferred, w_rows)); for diagnostics that
+   read the workspace.  A list is [N] i32 entries (home in bits 0-27), then its length and a take
+   counter.  int_mode round / fail: the layout (cell_rows hold rows only when dims.n_rp > 1);
+   round_lp: the back-pointers alone, every other field equals `total`; relax: all zero. */
+typedef struct dragg_mpc_workspace_regions {
+    int64_t back_pointers, solutions, deferred, big_rows, steps_list, steps_pools, mid_list, mid_rows, w_rows,
+            cell_rows, total;
+} dragg_mpc_workspace_regions;
+/* Host-only query; returns dragg_mpc_workspace_bytes' error codes. */
+int dragg_mpc_workspace_regions_get(const dragg_mpc_dims* dims, dragg_mpc_workspace_regions* regions);
+
 /* The sha-256 of the sources this library was built from (the kernel file and this header; since
    v9): the host refuses a library whose stamp is not its sources' (a stale build). */
 const char* dragg_mpc_source_hash(void);

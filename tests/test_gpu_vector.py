@@ -336,9 +336,6 @@ def test_sub_steps_4(gpu):
     b = va.batch
     steps = ((b.int_path & L.PATH_STEPS) != 0).nonzero().reshape(-1).cpu().tolist()
     assert any(h >= 16 for h in steps) and any(h < 16 for h in steps)
-    torch.cuda.synchronize()
-    r = L.workspace_regions(b.N, b.H, cells=b.dims.n_rp > 1)
-    lst = b.workspace.view(torch.uint8)[r["steps_list"]:r["steps_list"] + 4 * (b.N + 1)].view(torch.int32).cpu().numpy()
-    n = int(lst[b.N])
+    lst, n = b.work_list("steps_list")
     assert 0 < n <= b.N
-    assert sorted(set(int(x) & 0x0FFFFFFF for x in lst[:n])) == steps
+    assert sorted(set(int(x) & L.LIST_HOME_MASK for x in lst)) == steps

@@ -46,7 +46,8 @@ def test_ctypes_structs_match_c_layout(tmp_path):
     """sizeof/offsetof of every ABI struct, from gcc, against the ctypes mirrors."""
     from dragg_amd import _lib as L
     structs = {"dragg_mpc_dims": L.Dims, "dragg_mpc_problem": L.Problem, "dragg_mpc_hash": L.Hash,
-               "dragg_mpc_out": L.Out, "dragg_mpc_explicit": L.Explicit}
+               "dragg_mpc_out": L.Out, "dragg_mpc_explicit": L.Explicit,
+               "dragg_mpc_workspace_regions": L.WorkspaceRegions}
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(void){']
     for cname, cls in structs.items():
         lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
@@ -203,6 +204,11 @@ def test_size_queries_without_gpu(lib_path):
     # then (256-aligned) the front DP's LP cost-to-go rows [N][H + 1][64] (x, v)
     w_off = (mr_off + 2048 * 24 * 384 * 2 + 255) // 256 * 256
     assert ws == (w_off + 100 * 25 * 64 * 16 + 255) // 256 * 256
+    # every intermediate above against the library's own map: this proves the order of the regions
+    r = L.workspace_regions(d)
+    assert (r["back_pointers"], r["solutions"], r["deferred"], r["big_rows"], r["steps_list"], r["steps_pools"],
+            r["mid_list"], r["mid_rows"], r["w_rows"], r["cell_rows"], r["total"]) == \
+        (0, par, defer, big_off, nl_off, nr_off, ml_off, mr_off, w_off, ws, ws)
     # the lag mode's side workspace: the lists and per-block scratch only, [defer, w_off)
     lib.dragg_mpc_side_workspace_bytes.restype = ctypes.c_int64
     assert lib.dragg_mpc_side_workspace_bytes(ctypes.byref(d)) == w_off - defer
@@ -213,10 +219,32 @@ def test_size_queries_without_gpu(lib_path):
     d.horizon = 24
     d.int_mode = L.INT_RELAX
     assert lib.dragg_mpc_workspace_bytes(ctypes.byref(d)) == 0
+    assert set(L.workspace_regions(d).values()) == {0}
     assert lib.dragg_mpc_lds_bytes(ctypes.byref(d)) > lds_direct
+    # round_lp: the back-pointers of its front DP alone, every other region starts at the total
+    d.int_mode = L.INT_ROUND_LP
+    assert lib.dragg_mpc_workspace_bytes(ctypes.byref(d)) == par
+    r = L.workspace_regions(d)
+    assert r.pop("back_pointers") == 0 and set(r.values()) == {par}
+    # the map is refused where the size is
+    regions = L.WorkspaceRegions()
     d.int_mode = 9
     assert lib.dragg_mpc_workspace_bytes(ctypes.byref(d)) < 0
+    assert lib.dragg_mpc_workspace_regions_get(ctypes.byref(d), ctypes.byref(regions)) == \
+        lib.dragg_mpc_workspace_bytes(ctypes.byref(d)) == -1
     d.int_mode = L.INT_ROUND
+    assert lib.dragg_mpc_workspace_regions_get(ctypes.byref(d), None) == -1
+    d.horizon = 160
+    assert lib.dragg_mpc_workspace_regions_get(ctypes.byref(d), ctypes.byref(regions)) == \
+        lib.dragg_mpc_workspace_bytes(ctypes.byref(d)) == -4
+    with pytest.raises(L.DraggError):
+        L.workspace_regions(d)
+    # a list entry's home field holds every home index the library accepts, and no more
+    d.horizon, d.n_homes = 24, L.LIST_HOME_MASK
+    assert lib.dragg_mpc_workspace_bytes(ctypes.byref(d)) > 0
+    d.n_homes = L.LIST_HOME_MASK + 1
+    assert lib.dragg_mpc_workspace_bytes(ctypes.byref(d)) == -1
+    d.n_homes = 100
     d.horizon = 400                                    # LP kernel's LDS is the binding limit
     d.int_mode = L.INT_RELAX
     assert lib.dragg_mpc_lds_bytes(ctypes.byref(d)) == -4
@@ -234,6 +262,23 @@ PINNED_SIZES = {1: (9712, 314328576, 314328576, 314050048),
                 48: (12720, 495091200, 505126400, 486540800),
                 96: (16928, 679699968, 699565568, 662701568),
                 143: (23120, 860462848, 889954048, 835192320)}
+
+
+# (N, H, cells) -> the workspace's region map (dragg_amd._lib.workspace_regions' values in order): the values
+# of the Python mirror of the kernel's offset chain, before the library answered the query itself
+PINNED_REGIONS = {
+    (5, 24, False): (0, 80640, 88320, 88576, 50420224, 50420480, 147413760, 147414016, 185162752, 185290752,
+                     185290752),
+    (5, 24, True): (0, 80640, 88320, 88576, 50420224, 50420480, 147413760, 147414016, 185162752, 185290752,
+                    185546752),
+    (100, 48, False): (0, 3225600, 3532800, 3533312, 104196608, 104197120, 414575616, 414576128, 490073600,
+                       495091200, 495091200),
+    (100, 48, True): (0, 3225600, 3532800, 3533312, 104196608, 104197120, 414575616, 414576128, 490073600,
+                      495091200, 505126400),
+    (1000, 96, False): (0, 64512000, 70656000, 70660096, 271986688, 271990784, 582369280, 582373376, 733368320,
+                        832696320, 832696320),
+    (1000, 96, True): (0, 64512000, 70656000, 70660096, 271986688, 271990784, 582369280, 582373376, 733368320,
+                       832696320, 1031352320)}
 
 
 @pytest.mark.parametrize("H", sorted(PINNED_SIZES))
@@ -266,12 +311,14 @@ def test_largest_accepted_horizons(lib_path):
 @pytest.mark.parametrize("N,H", [(5, 24), (100, 48), (1000, 96)])
 @pytest.mark.parametrize("cells", [False, True])
 def test_workspace_regions_match_the_library(lib_path, N, H, cells):
-    """dragg_amd._lib.workspace_regions against the library's two size queries (totals and the side span do
-    not prove the order of the regions: tests/test_gpu_workspace_regions.py reads the lists)."""
+    """The library's region map (dragg_amd._lib.workspace_regions) against its pinned numbers and the library's
+    two size queries (test_size_queries_without_gpu proves the order of the regions from literal arithmetic,
+    tests/test_gpu_workspace_regions.py reads the lists)."""
     from dragg_amd import _lib as L
     lib = L.load()
     d = _round_dims(L, N, H, n_rp=H if cells else 1)
-    r = L.workspace_regions(N, H, cells)
+    r = L.workspace_regions(d)
+    assert tuple(r.values()) == PINNED_REGIONS[N, H, cells]
     assert r["total"] == lib.dragg_mpc_workspace_bytes(ctypes.byref(d))
     assert r["w_rows"] - r["deferred"] == lib.dragg_mpc_side_workspace_bytes(ctypes.byref(d))
     keys = list(r)

@@ -31,14 +31,13 @@ total = bargs.warmup + bargs.steps
 agg = DeviceAggregator(homes, oat, ghi, tou, 0, total, reward_price=[0.0], int_mode=bargs.int_mode, seed=12,
                        keep_history=not bargs.no_history)
 N, H = agg.batch.N, agg.batch.H
-par = L.workspace_regions(N, H)["solutions"]   # (the back-pointer rows come before the solutions)
 kids_tot, fT, fW, n_ran = 0.0, [], [], 0
 for t in range(total):
     agg.run_iteration()
     if t < bargs.warmup:
         continue
     torch.cuda.synchronize()
-    x = agg.batch.workspace.view(torch.uint8)[par:par + N * 8 * H * 8].view(torch.float64).view(N, H, 8)[:, :, 7]
+    x = agg.batch.solution_rows()[:, :, 7]
     v = x.cpu().numpy().copy()
     st = agg.batch.status.cpu().numpy()
     ran = (st == L.ST_OPTIMAL) | (st == L.ST_ROUND_FAIL)

@@ -7,11 +7,9 @@ import os
 import sys
 
 import numpy as np
-import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from dragg_amd._lib import workspace_regions                        # noqa: E402
 from dragg_amd.aggregator import DeviceAggregator                   # noqa: E402
 from dragg_amd.community import synthetic_homes, synthetic_weather  # noqa: E402
 
@@ -25,18 +23,14 @@ days = math.ceil((math.ceil(a.steps / dt) + hh + 2) / 24) + 1
 homes = synthetic_homes(a.homes, seed=12, days=days, dt=dt, horizon_hours=hh)
 oat, ghi, tou = synthetic_weather(days, dt, math.ceil(a.steps / dt), seed=3, month=7)
 agg = DeviceAggregator(homes, oat, ghi, tou, 0, a.steps, reward_price=[0.0], seed=12, keep_history=False)
-N, H = agg.batch.N, agg.batch.H
-regions = workspace_regions(N, H)
-offs = [regions[k] for k in ("deferred", "mid_list", "steps_list")]
+H = agg.batch.H
 rng = np.random.default_rng(5)
 tot = np.zeros(3, int)
 for t in range(a.steps):
     if a.rl:
         agg.set_reward_price(rng.uniform(-0.02, 0.02) - 0.03 * np.cos(np.arange(H) / 3.0))
     agg.run_iteration()
-    torch.cuda.synchronize()
-    ws = agg.batch.workspace.view(torch.uint8)
-    c = [int(ws[o + 4 * N:o + 4 * N + 4].view(torch.int32).item()) for o in offs]
+    c = [agg.batch.work_list(k)[1] for k in ("deferred", "mid_list", "steps_list")]
     tot += c
     print(f"t={t}: deferred {c[0]}, to big {c[1]}, to step DP {c[2]}", flush=True)
 print(f"total over {a.steps} steps: deferred {tot[0]}, to big {tot[1]}, to step DP {tot[2]}")

@@ -30,13 +30,12 @@ homes = synthetic_homes(a.homes, seed=12, days=days, dt=dt, horizon_hours=hh)
 oat, ghi, tou = synthetic_weather(days, dt, math.ceil(a.steps / dt), seed=3, month=7)
 agg = DeviceAggregator(homes, oat, ghi, tou, 0, a.steps, reward_price=[0.0], seed=12, keep_history=False,
                        rank=a.rank, world=a.world)
-N, H = agg.batch.N, agg.batch.H
-par = L.workspace_regions(N, H)["solutions"]
+N = agg.batch.N
 acc = []
 for t in range(a.steps):
     agg.run_iteration()
     torch.cuda.synchronize()
-    x = agg.batch.workspace.view(torch.uint8)[par:par + N * 8 * H * 8].view(torch.float64).view(N, H, 8)[:, :9, 7]
+    x = agg.batch.solution_rows()[:, :9, 7]
     st = agg.batch.status.cpu().numpy()
     v = x.cpu().numpy().copy()
     acc.append(v[st == L.ST_OPTIMAL])

@@ -27,12 +27,10 @@ days = math.ceil((math.ceil(a.steps / dt) + hh + 2) / 24) + 1
 homes = synthetic_homes(a.homes, seed=12, days=days, dt=dt, horizon_hours=hh)
 oat, ghi, tou = synthetic_weather(days, dt, math.ceil(a.steps / dt), seed=3, month=7)
 agg = DeviceAggregator(homes, oat, ghi, tou, 0, a.steps, reward_price=[0.0], seed=12, keep_history=False)
-N, H = agg.batch.N, agg.batch.H
-par = L.workspace_regions(N, H)["solutions"]
 rows = []
 names = ["feas", "lpdom", "cutpass", "recov", "sum_np", "max_np", "global", "flags", "sum_Mc", "ub_ext", "ub", "ranges", "-", "compact", "vstage", "merge", "values"]
 for t in range(a.steps):
-    ws = agg.batch.workspace.view(torch.uint8)[par:par + N * 8 * H * 8].view(torch.float64).view(N, H, 8)
+    ws = agg.batch.solution_rows()
     ws[:, 10:27, 7] = 0.0
     t0 = torch.cuda.Event(enable_timing=True)
     t1 = torch.cuda.Event(enable_timing=True)
