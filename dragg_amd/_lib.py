@@ -135,7 +135,7 @@ EXPORTS = ["dragg_mpc_abi_version", "dragg_mpc_strerror", "dragg_mpc_lds_bytes",
            "dragg_mpc_lag_reset", "dragg_mpc_step_main", "dragg_mpc_step_side", "dragg_mpc_aggregate_rows",
            "dragg_mpc_side_workspace_bytes", "dragg_mpc_side_grid", "dragg_mpc_source_hash",
            "dragg_mpc_replicate", "dragg_mpc_aggregate_groups", "dragg_mpc_step_episodes",
-           "dragg_mpc_season_noise_episodes"]
+           "dragg_mpc_season_noise_episodes", "dragg_mpc_adopt", "dragg_mpc_select_groups"]
 
 _LIB = None
 
@@ -201,6 +201,10 @@ def load(path=LIB_PATH):
                                             ctypes.POINTER(Hash), ctypes.POINTER(Out), ctypes.c_int32, c_dp, c_dp]
     lib.dragg_mpc_season_noise_episodes.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Episodes), ctypes.c_int32,
                                                     ctypes.c_int32, ctypes.c_int32, c_dp, c_dp]
+    lib.dragg_mpc_adopt.argtypes = [ctypes.POINTER(Dims), ctypes.c_int32, c_dp, ctypes.POINTER(Hash), ctypes.POINTER(Out),
+                                    ctypes.POINTER(Hash), ctypes.POINTER(Out), c_dp]
+    lib.dragg_mpc_select_groups.argtypes = [ctypes.POINTER(Dims), ctypes.c_int32, c_dp, c_dp, c_dp, ctypes.c_int32,
+                                            c_dp, c_dp]
     if lib.dragg_mpc_abi_version() != ABI_VERSION:
         raise DraggError("ABI version mismatch between dragg_amd and libdragg_mi355x.so")
     if not os.environ.get("DRAGG_LIB"):

@@ -34,6 +34,19 @@ def shard_index(n, rank, world):
     return np.arange(rank, n, world)
 
 
+class HeldStep:
+    """A sweep's first step, cloned out of its replica batch before the replicas move on: the arrays
+    `MPCBatch.adopt_from` reads."""
+
+    def __init__(self, rb, row):
+        self.N, self.H, self.groups, self.hist_row = rb.N, rb.H, getattr(rb, "groups", 1), row
+        # (fc is a view of fc_store where a batch has one: MPCBatch)
+        for k in ("vals", "fc_store", "status", "iters", "obj", "relax_obj", "int_path"):
+            v = getattr(rb, k, None)
+            setattr(self, k, v.clone() if v is not None else None)
+        self.fc = self.fc_store.permute(1, 2, 0) if self.fc_store is not None else rb.fc.clone()
+
+
 class DeviceAggregator:
     def __init__(self, homes, oat, ghi, tou, start_index=0, num_timesteps=96, reward_price=(0.0,),
                  int_mode="round", seed=0, rank=0, world=1, group=None, keep_history=True,
@@ -57,6 +70,11 @@ class DeviceAggregator:
         self.batch = batch_cls(self.homes, oat, ghi, tou, start_index, reward_price, **self._batch_kw)
         self._sweep_batches = {}     # G -> the G-replica batch of sweep()
         self.sweep_counts = None
+        # a held sweep (sweep(hold=True)): its first step's replicas, kept for commit(); `_gen` counts the
+        # moves of the live state (a step, a restore, a loaded checkpoint, a commit), which void a hold
+        self._hold = None
+        self._gen = 0
+        self._choices = {}           # G -> arange(G) int32 on the device (commit's choice is a view of it)
         self.num_timesteps = num_timesteps
         self.timestep = 0
         n = self.batch.N
@@ -141,6 +159,7 @@ class DeviceAggregator:
     # aggregator.py:711-726
     def run_iteration(self, noise=None):
         t = self.timestep
+        self._gen += 1
         hist = self.hist[t] if self.hist is not None else None
         if self.overlap and noise is None and self._lag_now(t):
             ring = self.ring is not None
@@ -251,6 +270,7 @@ class DeviceAggregator:
     def restore(self, snap):
         self.drain()
         t, vals, fc = snap
+        self._gen += 1
         self.timestep = t
         self.batch.vals.copy_(vals)
         self.batch.fc.copy_(fc)
@@ -291,7 +311,7 @@ class DeviceAggregator:
             rb.dims.n_env = self.batch.dims.n_env
         return rb
 
-    def sweep(self, prices, steps, noise_fn=None, src=0):
+    def sweep(self, prices, steps, noise_fn=None, src=0, hold=False):
         """The community's response to each of G candidate reward-price lists (`prices` [G][n], n == 1
         or n >= H) over `steps` timesteps ahead, nothing committed: a device tensor [G][steps][agg_load,
         forecast_load, agg_cost], row g bit-identical to `forecast(steps)` under prices[g], all-reduced
@@ -304,8 +324,14 @@ class DeviceAggregator:
         Device memory: the replica batch is kept (one per G): dragg_mpc_workspace_bytes at G * n homes
         plus its hash arrays (vals 19 x G n, fc G n x 15 x H fp64) and parameter rows -- at 10k homes,
         H = 48 and G = 8 under a price list 15.4 GB of workspace and 0.47 GB of hash arrays
-        (profiles/r07/sweep/sweep_line.json)."""
+        (profiles/r07/sweep/sweep_line.json).
+        hold=True: the replicas' first step -- the step `run_iteration` would take under each candidate, bit
+        for bit -- is kept with its history row, so that `commit(g)` can adopt replica g as the live
+        batch's step instead of solving it again.  With steps == 1 the replica batch itself holds it; with
+        more steps its arrays are cloned after the first step, before the replicas move on.  The hold lasts
+        until the live state moves or another sweep replaces it."""
         self.drain()
+        self._hold = None
         P = L.device_f64(prices, self.device)
         if P.dim() != 2 or P.shape[0] < 1:
             raise ValueError(f"sweep takes prices [G][n], not {list(P.shape)}")
@@ -318,17 +344,63 @@ class DeviceAggregator:
         rb.replicate_from(self.batch)
         out = torch.zeros((G, steps, 3), dtype=torch.float64, device=self.device)
         counts = torch.zeros((3, G), dtype=torch.int64, device=self.device)
+        row = None
+        if hold and steps > 0:
+            row = torch.full((L.NVAL, rb.N), float("nan"), dtype=torch.float64, device=self.device)
+            rb.hist_row = row
         for s in range(steps):
             t = self.timestep + s
-            rb.step(t, noise=noise_fn(t) if noise_fn else None, hist=None)
+            rb.step(t, noise=noise_fn(t) if noise_fn else None, hist=row if s == 0 else None)
             out[:, s].copy_(rb.aggregate_groups())
             if hasattr(rb, "int_path"):
                 counts += L.path_counts(rb.int_path.view(G, -1), 1)
+            if s == 0 and row is not None:
+                self._hold = {"t": self.timestep, "G": G, "P": P, "gen": self._gen,
+                              "src": rb if steps == 1 else HeldStep(rb, row)}
         if self.world > 1:
             torch.distributed.all_reduce(out, group=self.group)
             torch.distributed.all_reduce(counts, group=self.group)
         self.sweep_counts = dict(zip(L.PATH_COUNT_KEYS, counts.cpu().tolist()))
         return out
+
+    def holds(self, g=None):
+        """Is a held sweep still the live state's next step (and `g` one of its candidates)?"""
+        h = self._hold
+        return (h is not None and not self.overlap and h["gen"] == self._gen and h["t"] == self.timestep
+                and (g is None or 0 <= int(g) < h["G"]))
+
+    def commit(self, g):
+        """Play candidate g of the held sweep: its solved first step becomes step t of the live batch, as
+        `set_reward_price(prices[g]); run_iteration()` would have left it, bit for bit -- one copy kernel
+        (dragg_mpc_adopt) instead of the solve.  The live reward price becomes the sweep's broadcast row g;
+        vals, fc, status, iters, obj, relax_obj and int_path are replica g's, its history row goes to
+        hist[t], status_hist[t] and path_hist[t] are filed and the timestep advances; `collect_data()`
+        follows as after `run_iteration()`.  With more than one rank every rank passes the same g (as it
+        passes the same price) and adopts its own shard's replica: nothing is exchanged.  The hold is
+        dropped.  ValueError: no hold, g outside [0, G), the live state has moved since the sweep
+        (run_iteration, restore, load_state / resume, another commit), or lag mode (overlap=True)."""
+        if self.overlap:
+            raise ValueError("commit: lag mode (overlap=True) has no grouped batches to adopt from")
+        h = self._hold
+        if h is None:
+            raise ValueError("commit: no sweep is held (sweep(..., hold=True) first)")
+        if not 0 <= int(g) < h["G"]:
+            raise ValueError(f"commit: candidate {g} of a sweep of {h['G']}")
+        if h["gen"] != self._gen or h["t"] != self.timestep:
+            raise ValueError("commit: the live state has moved since the sweep was held")
+        t, G = self.timestep, h["G"]
+        self.drain()
+        self.batch.set_reward_price(h["P"][int(g)].clone())
+        ch = self._choices.get(G)
+        if ch is None:
+            ch = self._choices[G] = torch.arange(G, dtype=torch.int32, device=self.device)
+        self.batch.adopt_from(h["src"], ch[int(g):int(g) + 1], hist=self.hist[t] if self.hist is not None else None)
+        self.status_hist[t].copy_(self.batch.status, non_blocking=True)
+        if hasattr(self.batch, "int_path"):
+            self.path_hist[t].copy_(self.batch.int_path, non_blocking=True)
+        self.timestep += 1
+        self._gen += 1
+        self._hold = None
 
     # ------------------------------------------------------------------ checkpoint / resume
     # The reference has no resume (aggregator.py:265-267, 768: a stopped run starts over); here a
@@ -367,6 +439,7 @@ class DeviceAggregator:
         t = int(st["timestep"])
         if not 0 <= t <= self.num_timesteps:
             raise ValueError(f"checkpoint {path} holds timestep {t} of a {self.num_timesteps}-step run")
+        self._gen += 1
         self.batch.vals.copy_(st["vals"])
         self.batch.fc.copy_(st["fc"])
         self.batch.set_reward_price(st["reward_price"].to(self.device))

@@ -5062,6 +5062,78 @@ __global__ __launch_bounds__(REP_NT) void replicate_kernel(RepSeg a, RepSeg b, i
     }
 }
 
+// The way back (dragg_mpc_adopt): the destination batch's E groups of Nb homes each take, from a source
+// that holds C copies of the destination (copy-major: replicate_kernel's layout with G = C), the columns
+// of copy choice[e].  Every array is a segment: `rows` rows whose columns are `elem` bytes wide (vals / hist:
+// NVAL rows of 8, obj / relax_obj: one row of 8, status / iters / int_path: one row of 4, fc: one row of
+// NFC * H * 8 -- a home's block).  Group e's part of a row is Nb * elem bytes at column e * Nb of the
+// destination and column c * Nd + e * Nb of the source (Nd = E * Nb).  A unit is the widest of 16 / 8 / 4
+// bytes that divides both bases, Nb * elem and Nd * elem (then every group's offset in every copy and
+// both row strides are aligned).  Block (x, e) works on group e alone, so choice[e] is block-uniform: a
+// choice outside [0, C) ends the block before any access.  Lanes on consecutive units; the bits move
+// through integer registers.
+constexpr int ADOPT_NSEG = 8;
+struct AdoptSeg {
+    const char* src;
+    char* dst;
+    long long src_stride, dst_stride;   // bytes between rows
+    long long elem;                     // bytes per column
+    long long row_units;                // units of one group's part of a row (Nb * elem / the unit's bytes)
+    long long end;                      // units of this and every earlier segment, per group
+    int unit;                           // bytes: 16, 8 or 4
+    int rows;
+};
+struct AdoptArgs {
+    AdoptSeg seg[ADOPT_NSEG];
+    int nseg;
+    int copies;
+    long long Nb, Nd;
+    const int32_t* choice;
+};
+template <typename T>
+DEV void adopt_copy(const AdoptSeg& s, long long u, long long src_col, long long dst_col) {
+    const long long r = s.rows == 1 ? 0 : u / s.row_units, i = u - r * s.row_units;
+    const T* p = reinterpret_cast<const T*>(s.src + r * s.src_stride + src_col * s.elem) + i;
+    T* q = reinterpret_cast<T*>(s.dst + r * s.dst_stride + dst_col * s.elem) + i;
+    *q = *p;
+}
+__global__ __launch_bounds__(REP_NT) void adopt_kernel(AdoptArgs a) {
+    const int e = (int)blockIdx.y;
+    const int c = __builtin_amdgcn_readfirstlane(a.choice[e]);
+    if (c < 0 || c >= a.copies) return;
+    const long long dst_col = (long long)e * a.Nb, src_col = (long long)c * a.Nd + dst_col;
+    const long long n = a.seg[a.nseg - 1].end;
+    for (long long x = (long long)blockIdx.x * REP_NT + threadIdx.x; x < n; x += (long long)gridDim.x * REP_NT) {
+        int k = 0;
+        while (x >= a.seg[k].end) ++k;
+        const AdoptSeg& s = a.seg[k];
+        const long long u = x - (k ? a.seg[k - 1].end : 0);
+        if (s.unit == 16) adopt_copy<uint4>(s, u, src_col, dst_col);
+        else if (s.unit == 8) adopt_copy<unsigned long long>(s, u, src_col, dst_col);
+        else adopt_copy<unsigned>(s, u, src_col, dst_col);
+    }
+}
+
+// dragg_mpc_select_groups: lane e picks, for group e, the copy whose load (sums[c * E + e][0]) lies closest
+// to target[e]; ties to the smaller |prices[c * E + e][0]|, then to the smaller c (a later copy must be
+// strictly better).  A NaN load is never chosen; none valid: -1.
+__global__ void select_groups_kernel(int E, int C, const double* sums, const double* target, const double* prices,
+                                     int n_rp, int32_t* choice) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const double sp = target[e];
+    int best = -1;
+    double bd = 0.0, bp = 0.0;
+    for (int c = 0; c < C; ++c) {
+        const size_t k = (size_t)c * E + e;
+        const double load = sums[k * 3];
+        if (load != load) continue;
+        const double d = fabs(load - sp), p = fabs(prices[k * (size_t)n_rp]);
+        if (best < 0 || d < bd || (d == bd && p < bp)) { best = c; bd = d; bp = p; }
+    }
+    choice[e] = best;
+}
+
 // (nb: the base homes of a grouped batch, N otherwise.  Home r of group g = r / nb draws the stream of
 // (ep.seed[g] -- NULL: seed --, its base home, ep.timestep[g] -- NULL: t); the columns of a group whose own
 // timestep is negative are left as they are)
@@ -5618,6 +5690,60 @@ int dragg_mpc_replicate(const dragg_mpc_dims* dims, const dragg_mpc_hash* src_ha
     const long long blocks = (v.units + f.units + REP_NT - 1) / REP_NT;
     hipLaunchKernelGGL(replicate_kernel, dim3((unsigned)min(blocks, (long long)REP_BLOCKS_MAX)), dim3(REP_NT), 0,
                        (hipStream_t)stream, v, f, G);
+    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+}
+
+int dragg_mpc_adopt(const dragg_mpc_dims* dst_dims, int32_t copies, const int32_t* choice,
+                    const dragg_mpc_hash* src_hash, const dragg_mpc_out* src_out, dragg_mpc_hash* dst_hash,
+                    dragg_mpc_out* dst_out, void* stream) {
+    if (!dst_dims || dst_dims->n_homes < 0 || dst_dims->horizon < 1 || copies < 1 || !choice || !src_hash || !dst_hash)
+        return DRAGG_E_ARG;
+    const int E = group_count(dst_dims);
+    if (E < 0 || E > 65535) return DRAGG_E_ARG;       // (a grid row per group)
+    if (dst_dims->n_homes == 0) return DRAGG_OK;
+    if (!src_hash->vals || !src_hash->fc || !dst_hash->vals || !dst_hash->fc) return DRAGG_E_ARG;
+    const long long Nd = dst_dims->n_homes, Nb = Nd / E;
+    AdoptArgs a{};
+    a.copies = copies;
+    a.Nb = Nb;
+    a.Nd = Nd;
+    a.choice = choice;
+    auto seg = [&](const void* s, void* d, long long elem, int rows) {
+        if (!s || !d) return;              // a member either side leaves out
+        const uintptr_t bits = reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d) |
+                               (uintptr_t)(Nb * elem) | (uintptr_t)(Nd * elem);
+        const int unit = bits % 16 == 0 ? 16 : bits % 8 == 0 ? 8 : 4;
+        AdoptSeg& g = a.seg[a.nseg];
+        g = AdoptSeg{static_cast<const char*>(s), static_cast<char*>(d), (long long)copies * Nd * elem, Nd * elem,
+                     elem, Nb * elem / unit, 0, unit, rows};
+        g.end = (a.nseg ? a.seg[a.nseg - 1].end : 0) + rows * g.row_units;
+        ++a.nseg;
+    };
+    seg(src_hash->fc, dst_hash->fc, (long long)DRAGG_NFC * dst_dims->horizon * 8, 1);
+    seg(src_hash->vals, dst_hash->vals, 8, DRAGG_NVAL);
+    if (src_out && dst_out) {
+        seg(src_out->hist, dst_out->hist, 8, DRAGG_NVAL);
+        seg(src_out->obj, dst_out->obj, 8, 1);
+        seg(src_out->relax_obj, dst_out->relax_obj, 8, 1);
+        seg(src_out->status, dst_out->status, 4, 1);
+        seg(src_out->iters, dst_out->iters, 4, 1);
+        seg(src_out->int_path, dst_out->int_path, 4, 1);
+    }
+    const long long blocks = (a.seg[a.nseg - 1].end + REP_NT - 1) / REP_NT;
+    const long long cap = max(1LL, (long long)REP_BLOCKS_MAX / E);
+    hipLaunchKernelGGL(adopt_kernel, dim3((unsigned)min(blocks, cap), (unsigned)E), dim3(REP_NT), 0,
+                       (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+}
+
+int dragg_mpc_select_groups(const dragg_mpc_dims* dst_dims, int32_t copies, const double* sums, const double* target,
+                            const double* prices, int32_t n_rp, int32_t* choice, void* stream) {
+    if (!dst_dims || dst_dims->n_homes < 0 || copies < 1 || n_rp < 1 || !sums || !target || !prices || !choice)
+        return DRAGG_E_ARG;
+    const int E = group_count(dst_dims);
+    if (E < 0) return DRAGG_E_ARG;
+    hipLaunchKernelGGL(select_groups_kernel, dim3((E + 63) / 64), dim3(64), 0, (hipStream_t)stream, E, copies, sums,
+                       target, prices, n_rp, choice);
     return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
 }
 

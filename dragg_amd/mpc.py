@@ -161,6 +161,7 @@ class MPCBatch:
         self.relax_obj = torch.zeros(self.N, dtype=torch.float64, device=dev)
         self.int_path = torch.zeros(self.N, dtype=torch.int32, device=dev)
         self.agg = torch.zeros(3, dtype=torch.float64, device=dev)
+        self.hist_row = None        # a held sweep's history row ([NVAL][N], adopt_from reads it)
         self.cycles = None
         rc = self.lib.dragg_mpc_lds_bytes(ctypes.byref(self.dims))
         if rc < 0:
@@ -415,13 +416,67 @@ class MPCBatch:
     # ------------------------------------------------------------------ grouped batches
     def replicate_from(self, base, stream=None):
         """Copy `base`'s hash arrays (vals, fc: the state a step reads) into every replica of this
-        grouped batch, bit for bit, in one kernel (dragg_mpc_replicate).  `base` is only read."""
-        if base.N * self.groups != self.N or base.H != self.H:
+        grouped batch, bit for bit, in one kernel (dragg_mpc_replicate).  `base` is only read.  `base` may
+        itself be a grouped batch of E groups: this batch (C * E groups) then holds C copies of it,
+        copy-major -- copy c of base group e is group c * E + e."""
+        copies = self.groups // max(getattr(base, "groups", 1), 1)
+        if base.N * copies != self.N or copies * getattr(base, "groups", 1) != self.groups or base.H != self.H:
             raise ValueError(f"replicate_from: {self.groups} replicas of {self.Nb} homes (H = {self.H}) cannot "
                              f"take a batch of {base.N} homes (H = {base.H})")
         with torch.cuda.device(self.device):
             base.drain(stream)
-            self._call(self.lib.dragg_mpc_replicate, base._hash(), self._hash(), stream=stream)
+            dims = L.Dims.from_buffer_copy(self.dims)
+            dims.n_groups = copies if copies > 1 else 0
+            L.check(self.lib.dragg_mpc_replicate(dims, base._hash(), self._hash(), L.stream_ptr(stream, self.device)))
+
+    def adopt_from(self, src, choice, hist=None, stream=None):
+        """The way back (dragg_mpc_adopt): `src` holds C copies of this batch, copy-major (what
+        `replicate_from(self)` fills and a step then solves); group e of this batch takes the columns of copy
+        `choice[e]` -- vals, fc, status, iters, obj, relax_obj, int_path, and `src.hist_row` ([NVAL][C * N],
+        the history row the source's step wrote) into `hist` ([NVAL][N]) where both are given -- bit for
+        bit.  `choice`: a contiguous device int32 [E]; an entry outside [0, C) leaves its group untouched.
+        `src` is only read (an MPCBatch, or anything with its arrays: a clone of them).  No synchronisation."""
+        E = max(self.groups, 1)
+        copies = src.N // self.N if self.N else max(getattr(src, "groups", 1), 1) // E
+        if copies < 1 or src.N != copies * self.N or src.H != self.H:
+            raise ValueError(f"adopt_from: a batch of {self.N} homes (H = {self.H}) cannot adopt from "
+                             f"{src.N} homes (H = {src.H}): the source holds whole copies of it")
+        if not torch.is_tensor(choice) or choice.device != self.device or choice.dtype != torch.int32 \
+                or tuple(choice.shape) != (E,) or not choice.is_contiguous():
+            raise ValueError(f"choice must be a contiguous device tensor [{E}] of {torch.int32}, not "
+                             f"{getattr(choice, 'dtype', type(choice))} {list(getattr(choice, 'shape', []))}")
+        row = getattr(src, "hist_row", None)
+        with torch.cuda.device(self.device):
+            self.drain(stream)
+            src_out = L.Out(status=L.ptr(src.status), iters=L.ptr(src.iters), obj=L.ptr(src.obj),
+                            relax_obj=L.ptr(src.relax_obj), hist=L.ptr(row if hist is not None else None),
+                            cycles=None, int_path=L.ptr(src.int_path))
+            L.check(self.lib.dragg_mpc_adopt(self.dims, copies, L.ptr(choice),
+                                             L.Hash(vals=L.ptr(src.vals), fc=L.ptr(src.fc_store)), src_out,
+                                             self._hash(), self._out(hist if row is not None else None, timed=False),
+                                             L.stream_ptr(stream, self.device)))
+            self._keep = (src, choice, hist)
+
+    def select_groups(self, sums, target, prices, stream=None):
+        """The choice for `adopt_from`, made on the device (dragg_mpc_select_groups): `sums` [C * E][3]
+        (`aggregate_groups` of the copies' batch), `target` [E], `prices` [C * E][n] (its reward-price rows)
+        -> device int32 [E]: per group the copy whose load lies closest to the target, ties to the smaller
+        |price|, then the smaller copy; -1 where every load is NaN.  No synchronisation."""
+        E = max(self.groups, 1)
+        sums = L.device_f64(sums, self.device).contiguous()
+        target = L.device_f64(target, self.device).reshape(-1).contiguous()
+        prices = L.device_f64(prices, self.device)
+        if sums.dim() != 2 or sums.shape[1] != 3 or sums.shape[0] < E or sums.shape[0] % E or target.numel() != E:
+            raise ValueError(f"select_groups takes sums [C * {E}][3] and target [{E}], not {list(sums.shape)} "
+                             f"and {list(target.shape)}")
+        prices = prices.reshape(sums.shape[0], -1).contiguous()
+        with torch.cuda.device(self.device):
+            choice = torch.empty(E, dtype=torch.int32, device=self.device)
+            L.check(self.lib.dragg_mpc_select_groups(self.dims, sums.shape[0] // E, L.ptr(sums), L.ptr(target),
+                                                     L.ptr(prices), int(prices.shape[1]), L.ptr(choice),
+                                                     L.stream_ptr(stream, self.device)))
+            self._keep = (sums, target, prices)
+            return choice
 
     def aggregate_groups(self, stream=None):
         """collect_data's sums of every group -> device tensor [G][3]; row g is bit-identical to

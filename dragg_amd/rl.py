@@ -20,9 +20,16 @@ itself being the `env` it reads.
 none): a discrete PI controller on the relative forecast error against the aggregator's
 setpoint (`gen_setpoint`, aggregator.py:677-696), clipped to `rl.utility.action_space`.
 """
+from collections import namedtuple
+
 import numpy as np
 
 from ._lib import episode_mask
+
+# What a policy may return instead of a price after `rl_sweep(..., hold=True)`: candidate `index` of that
+# sweep, to be played by adopting its solved step (`Aggregator.rl_commit`), and its `price` (what
+# `rl_step` takes), played the ordinary way if the sweep is no longer held.
+Candidate = namedtuple("Candidate", ["index", "price"])
 
 
 def setpoint_update(state, timestep, agg_load, max_poss_load, prev_timesteps):
@@ -198,6 +205,25 @@ class VectorEnv:
             self._setpoint(e)
         return self.observations(), self.done()
 
+    def step_swept(self, candidates):
+        """`step` with the price chosen from C candidates per episode (`candidates` [E][C] or [E][C][n], $/kWh)
+        instead of guessed: every candidate of every active episode is solved one step ahead in one batch
+        (`VectorAggregator.sweep`), the one whose load lies closest to the episode's setpoint is chosen on
+        the device (`select`: ties to the smaller |price|, then the smaller index) and its solved step
+        adopted (`commit`) -- no second solve.  -> (observations, done [E]); `self.choice` holds the chosen
+        indices ([E] numpy, -1: the episode took no step)."""
+        on = ~self.parked & ~self.done()
+        sums = self.va.sweep(candidates)
+        choice = self.va.select(sums, self.agg_setpoint, candidates)
+        agg = self.va.commit(choice).cpu().numpy()
+        adopted = self.va.adopted.cpu().numpy()
+        self.choice = np.where(adopted, choice.cpu().numpy(), -1)
+        for e in np.flatnonzero(on & adopted):
+            self.timestep[e] += 1
+            self.agg_load[e], self.forecast_load[e], self.agg_cost[e] = agg[e]
+            self._setpoint(e)
+        return self.observations(), self.done()
+
 
 class SweepAgent:
     """Evaluates the price-response curve instead of guessing it: `n_candidates` actions evenly
@@ -205,11 +231,15 @@ class SweepAgent:
     in one grouped launch (`env.rl_sweep`, DeviceAggregator.sweep), and the price whose first
     forecast step's aggregate load lies closest to `env.agg_setpoint` is played; ties go to the
     smaller |price|.  `history` keeps every step's candidates, their responses (the first step's
-    aggregate load per candidate) and the choice."""
+    aggregate load per candidate) and the choice.  commit=True (`rl.parameters.commit`): the sweep is held
+    and `act` returns a `Candidate`, so that `run_rl_agg` plays the chosen candidate by adopting its solved
+    step instead of solving it again (`Aggregator.rl_commit`; the results are the same bit for bit)."""
 
     name = "sweep"
 
-    def __init__(self, config, n_candidates=8):
+    def __init__(self, config, n_candidates=8, commit=False):
+        self.commit = bool(commit)
+        self.index = None
         util = config["rl"]["utility"]
         lo, hi = util["action_space"]
         self.lo, self.hi = float(lo), float(hi)
@@ -222,19 +252,28 @@ class SweepAgent:
 
     def train(self, env):
         acts = self.candidates()
-        resp = np.asarray(env.rl_sweep([float(a) / self.scale for a in acts]), dtype=float)
+        prices = [float(a) / self.scale for a in acts]
+        resp = np.asarray(env.rl_sweep(prices, hold=True) if self.commit else env.rl_sweep(prices), dtype=float)
         load = resp[:, 0, 0] if resp.shape[1] else np.zeros(len(acts))   # (no step left in the run: all tie)
         sp = float(env.agg_setpoint)
         best = min(range(len(acts)), key=lambda i: (abs(load[i] - sp), abs(acts[i])))
         a = float(np.clip(acts[best], self.lo, self.hi))
+        self.index = best
         self.history["candidates"].append(acts.tolist())
         self.history["response"].append(load.tolist())
         self.history["action"].append(a)
         return a
 
     def act(self, env):
-        """policy(aggregator) -> reward price for `Aggregator.run_rl_agg`."""
-        return self.train(env) / self.scale
+        """policy(aggregator) -> reward price for `Aggregator.run_rl_agg` (commit=True: the `Candidate`)."""
+        p = self.train(env) / self.scale
+        return Candidate(self.index, p) if self.commit else p
+
+    def act_vector(self, env_obs):
+        """Observations of a `VectorEnv` -> candidate prices [E][C] for `VectorEnv.step_swept` (every episode
+        the same `candidates()`)."""
+        E = len(np.asarray(env_obs["agg_setpoint"]).reshape(-1))
+        return np.tile(self.candidates() / self.scale, (E, 1))
 
 
 def agent_policy(aggregator):
@@ -242,8 +281,10 @@ def agent_policy(aggregator):
     its own, `rl.parameters.kp` (default 1.0) and `rl.parameters.ki` (default 0.1).  The reference's
     `rl.parameters.learning_rate` (README.md:58-63) is a learning agent's step size, not a controller
     gain: it is left to an agent wrapped by `policy_from_agent`.  `rl.parameters.policy = "sweep"`
-    selects `SweepAgent` instead, with `rl.parameters.candidates` (default 8) candidate prices."""
+    selects `SweepAgent` instead, with `rl.parameters.candidates` (default 8) candidate prices;
+    `rl.parameters.commit = true` makes it play the chosen candidate by adopting its solved step."""
     p = aggregator.config.get("rl", {}).get("parameters", {}) or {}
     if p.get("policy") == "sweep":
-        return SweepAgent(aggregator.config, n_candidates=int(p.get("candidates", 8))).act
+        return SweepAgent(aggregator.config, n_candidates=int(p.get("candidates", 8)),
+                          commit=bool(p.get("commit", False))).act
     return SetpointAgent(aggregator.config, kp=float(p.get("kp", 1.0)), ki=float(p.get("ki", 0.1))).act

@@ -22,6 +22,7 @@ external driver).  SPP prices (`agg.spp_enabled`, an ERCOT xlsx absent from the 
 raise.
 """
 import json
+import logging
 import os
 import time
 import warnings
@@ -309,20 +310,56 @@ class Aggregator:
             self.dev.set_reward_price(prev)
         return out.cpu().numpy()
 
-    def rl_sweep(self, prices, steps=None):
+    def rl_sweep(self, prices, steps=None, hold=False):
         """The community's response to each of G candidate prices (scalars, or lists of
         action_horizon*dt values) over `rl.forecast_horizon` timesteps, all candidates solved together
         on device (`DeviceAggregator.sweep`): what G `rl_forecast` calls return, bit for bit, without
         their snapshots and restores.  Nothing is committed and `self.reward_price` stays.
         -> [G][steps][agg_load, forecast_load, agg_cost] on the host; the candidates' solve-path counts
-        are in `self.dev.sweep_counts`."""
+        are in `self.dev.sweep_counts`.  hold=True: the candidates' solved first step is kept, and
+        `rl_commit(g)` plays candidate g without solving it again."""
         steps = int(self.config["agg"]["rl"]["forecast_horizon"]) if steps is None else int(steps)
         steps = min(steps, self.num_timesteps - self.dev.timestep)
         rows = [self._price_list(p) for p in prices]
         if not rows:
             raise ValueError("rl_sweep needs at least one candidate price")
-        out = self.dev.sweep(np.stack(rows), steps, noise_fn=self._noise if getattr(self, "noise_fn", None) else None)
+        noise_fn = self._noise if getattr(self, "noise_fn", None) else None
+        if hold:
+            out = self.dev.sweep(np.stack(rows), steps, noise_fn=noise_fn, hold=True)
+            self._held_prices = rows
+        else:
+            out = self.dev.sweep(np.stack(rows), steps, noise_fn=noise_fn)
         return out.cpu().numpy()
+
+    def rl_commit(self, g):
+        """`rl_step` under candidate g of the held sweep (`rl_sweep(..., hold=True)`) with the solve replaced:
+        the price is published, replica g's solved step adopted as this timestep (`DeviceAggregator.commit`,
+        which installs the sweep's own price row: the live price ends as that row bit for bit), then
+        collect and the new setpoint as in `rl_step`.  ValueError (nothing changed) when the sweep is not
+        held any more or g is not one of its candidates."""
+        if not self.dev.holds(g):
+            raise ValueError(f"rl_commit({g}): no held sweep of the live state has that candidate")
+        self._set_price(self._held_prices[int(g)])
+        self.redis_set_current_values()
+        self.dev.commit(int(g))
+        self.timestep = self.dev.timestep
+        return self.collect_data()
+
+    def _play(self, action):
+        """One timestep under a policy's return value: a `rl.Candidate` of a held sweep is committed
+        (`rl_commit`), anything else -- or a candidate whose sweep is no longer held, logged once -- is
+        solved under its price (`rl_step`)."""
+        from .rl import Candidate
+        if not isinstance(action, Candidate):
+            return self.rl_step(action)
+        if self.dev.holds(action.index):
+            return self.rl_commit(action.index)
+        if not getattr(self, "_warned_hold", False):
+            self._warned_hold = True
+            logging.getLogger(__name__).warning(
+                "run_rl_agg: the policy returned a sweep candidate but the sweep is no longer held; "
+                "solving the step under its price instead (rl_step)")
+        return self.rl_step(action.price)
 
     # aggregator.py:898-911
     def test_response(self):
@@ -337,13 +374,15 @@ class Aggregator:
         """The `run_rl_agg` case (README.md:55): MPC homes under an RL-designed reward price.
         `policy(aggregator) -> reward price` is called once per timestep (e.g. an
         `dragg_amd.rl.SetpointAgent.act`, or the reference's agent via `rl.policy_from_agent`);
-        it may call `rl_forecast` to try a candidate price, or `rl_sweep` to try several at once.
+        it may call `rl_forecast` to try a candidate price, or `rl_sweep` to try several at once; after
+        `rl_sweep(..., hold=True)` it may return a `rl.Candidate` instead, which is played by adopting its
+        already solved step (`rl_commit`).
         Writes `<run dir>/rl_agg/results.json` with the Summary's RP and p_grid_setpoint."""
         self.case = "rl_agg"
         self.get_homes()
         self.setup_rl_agg_run(noise_fn)
         for t in range(self.num_timesteps):
-            self.rl_step(policy(self))
+            self._play(policy(self))
             if (t + 1) % self.checkpoint_interval == 0:
                 # the reference raises inside the step that fails (mpc_calc.py:280-289,
                 # 537-539); checking at each checkpoint (one host sync) keeps post-error data

@@ -58,6 +58,12 @@ class VectorAggregator:
         self.status_hist = torch.zeros((T, N), dtype=torch.int32, device=dev)
         self.path_hist = torch.zeros((T, N), dtype=torch.int32, device=dev)
         self.agg_hist = torch.zeros((T, E, 3), dtype=torch.float64, device=dev)
+        self._batch_args = (batch_cls, dict(int_mode=int_mode, device=dev, **batch_kw))
+        self._sweep_batches = {}     # C -> the C * E-group batch of sweep()
+        # a held sweep (sweep -> commit) and the moves of the live state that void it (step, reset, commit)
+        self._hold = None
+        self._gen = 0
+        self.adopted = torch.zeros(E, dtype=torch.bool, device=dev)      # the episodes the last commit advanced
 
     # ------------------------------------------------------------------ masks and keys
     def _mask(self, mask):
@@ -102,6 +108,7 @@ class VectorAggregator:
         batch: the step at t = 0 takes its initial conditions from the parameters), history rows cleared,
         active.  `seeds` / `start_indices` ([E]): new keys, taken for the masked episodes only."""
         m = self._mask(mask)
+        self._gen += 1
         self._set_keys(None if mask is None else m, seeds, start_indices)
         hm = self._homes_mask(m)
         b = self.batch
@@ -153,6 +160,7 @@ class VectorAggregator:
         if P.dim() != 2 or P.shape[0] != self.E:
             raise ValueError(f"step takes prices [{self.E}] or [{self.E}][n], not {list(P.shape)}")
         b = self.batch
+        self._gen += 1
         b.set_reward_price(P.contiguous())
         on = self.active()
         eff = torch.where(on, self.clocks, torch.full_like(self.clocks, -1))
@@ -161,6 +169,13 @@ class VectorAggregator:
             # fresh history row)
             self._row.fill_(float("nan"))
         b.step_episodes(self.seeds, self.starts, eff, noise=noise, hist=self._row)
+        self._keep = eff
+        return self._file(on)
+
+    def _file(self, on):
+        """After a step of the episodes `on` (solved, or adopted): their sums, the step's rows filed at each
+        episode's own clock, the clocks advanced.  -> [E][3]"""
+        b = self.batch
         agg = b.aggregate_groups()
         idx = self.clocks.clamp(0, self.num_timesteps - 1).to(torch.int64)
         if self.hist is not None:
@@ -172,8 +187,94 @@ class VectorAggregator:
         ai = idx.view(1, self.E, 1).expand(1, self.E, 3)
         a.scatter_(0, ai, torch.where(on.view(1, self.E, 1), agg.view(1, self.E, 3), a.gather(0, ai)))
         self.clocks = self.clocks + on.to(torch.int32)
-        self._keep = eff
         return agg
+
+    # ------------------------------------------------------------------ sweep, select, commit
+    # C candidate prices per episode, one step ahead: a batch of C * E groups holds C copies of the live
+    # E-group batch, copy-major (group c * E + e = episode e under its candidate c), filled by
+    # dragg_mpc_replicate and stepped once with the episodes' keys and clocks tiled C times.  `commit` then
+    # adopts, per episode, the chosen copy's solved step (dragg_mpc_adopt) instead of solving it again; the
+    # choice can be made on the device (`select`), so none of this synchronises with the host.
+    def _sweep_batch(self, C):
+        rb = self._sweep_batches.get(C)
+        if rb is None:
+            cls, kw = self._batch_args
+            rb = cls(self.homes, None, None, None, 0, (0.0,), groups=C * self.E, **kw)
+            self._sweep_batches[C] = rb
+        for k in ("oat", "ghi", "tou", "start_index"):           # the live batch's environment (the same tensors)
+            if hasattr(self.batch, k):
+                setattr(rb, k, getattr(self.batch, k))
+        if hasattr(self.batch, "dims"):
+            rb.dims.n_env = self.batch.dims.n_env
+        return rb
+
+    def sweep(self, prices, hold=True):
+        """Every active episode's next step under each of its C candidate prices (`prices` [E][C], or
+        [E][C][n] with n == 1 or n >= H), nothing committed -> device tensor [E][C][3], row (e, c)
+        bit-identical to what `step` returns for episode e under prices[e][c] (an idle episode's rows: its
+        state's sums).  One step ahead only.  The live batch is only read.  hold=True (default) keeps the
+        solved replicas for `commit`."""
+        P = L.device_f64(prices, self.device)
+        if P.dim() == 2:
+            P = P.unsqueeze(-1)
+        if P.dim() != 3 or P.shape[0] != self.E or P.shape[1] < 1:
+            raise ValueError(f"sweep takes prices [{self.E}][C] or [{self.E}][C][n], not {list(P.shape)}")
+        C = int(P.shape[1])
+        Pc = P.permute(1, 0, 2).contiguous()                     # copy-major: [C][E][n]
+        self._hold = None
+        rb = self._sweep_batch(C)
+        rb.set_reward_price(Pc.view(C * self.E, -1))
+        rb.replicate_from(self.batch)
+        on = self.active()
+        eff = torch.where(on, self.clocks, torch.full_like(self.clocks, -1))
+        if hold and self._row is not None:
+            if getattr(rb, "hist_row", None) is None:
+                rb.hist_row = torch.empty((L.NVAL, rb.N), dtype=torch.float64, device=self.device)
+            rb.hist_row.fill_(float("nan"))
+        keys = (self.seeds.repeat(C), self.starts.repeat(C), eff.repeat(C))
+        rb.step_episodes(*keys, hist=rb.hist_row if hold and self._row is not None else None)
+        sums = rb.aggregate_groups().view(C, self.E, 3)
+        if hold:
+            self._hold = {"C": C, "P": Pc, "gen": self._gen, "on": on, "src": rb, "keys": keys}
+        return sums.permute(1, 0, 2).contiguous()
+
+    def select(self, sums, setpoints, prices):
+        """Per episode the candidate whose load (`sums` [E][C][3], `sweep`'s) lies closest to its setpoint
+        (`setpoints` [E]); ties to the smaller |price| (`prices` [E][C] or [E][C][n]: its first entry), then the
+        smaller index; -1 where no candidate has a load -> device int32 [E] (dragg_mpc_select_groups)."""
+        S = L.device_f64(sums, self.device)
+        P = L.device_f64(prices, self.device)
+        if S.dim() != 3 or S.shape[0] != self.E or S.shape[2] != 3:
+            raise ValueError(f"select takes sums [{self.E}][C][3], not {list(S.shape)}")
+        C = int(S.shape[1])
+        P = P.reshape(self.E, C, -1).permute(1, 0, 2).reshape(C * self.E, -1)
+        return self.batch.select_groups(S.permute(1, 0, 2).reshape(C * self.E, 3), setpoints, P)
+
+    def commit(self, choice):
+        """Play, per episode, candidate choice[e] of the held sweep (`choice`: a device int tensor [E]): its
+        solved step becomes the episode's step, as `step` under the chosen price rows would have left it, bit
+        for bit.  An entry outside [0, C) -- and every episode that was idle in the sweep or is idle now --
+        adopts nothing and stays where it is.  The chosen rows become the live batch's reward price (an
+        episode that adopted nothing: its candidate 0's row, which nothing reads).  -> [E][3], the episodes'
+        sums as `step` returns them; `self.adopted` (device bool [E]) holds the episodes that advanced."""
+        h = self._hold
+        if h is None or h["gen"] != self._gen:
+            raise ValueError("commit: no sweep of the live state is held (sweep first; a step or a reset voids it)")
+        C, rb, b = h["C"], h["src"], self.batch
+        if not torch.is_tensor(choice) or tuple(choice.shape) != (self.E,) or choice.dtype.is_floating_point:
+            raise ValueError(f"commit takes a device int tensor [{self.E}]")
+        self._hold = None
+        ch = choice.to(device=self.device, dtype=torch.int32)
+        on = h["on"] & self.active() & (ch >= 0) & (ch < C)
+        ch = torch.where(on, ch, torch.full_like(ch, -1)).contiguous()
+        self._gen += 1
+        rows = h["P"][ch.clamp(0, C - 1).to(torch.int64), torch.arange(self.E, device=self.device)]
+        b.set_reward_price(rows.contiguous())
+        if self._row is not None:
+            self._row.fill_(float("nan"))
+        b.adopt_from(rb, ch, hist=self._row)
+        self.adopted = on
+        return self._file(on)
 
     # ------------------------------------------------------------------ rows for the host
     def clocks_host(self):

@@ -335,6 +335,31 @@ int dragg_mpc_aggregate(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, 
 int dragg_mpc_replicate(const dragg_mpc_dims* dims, const dragg_mpc_hash* src_hash,
                         dragg_mpc_hash* dst_hash, void* stream);
 
+/* The way back: adopt one of C copies as the destination batch's state (since v10, additive).  `dst_dims`
+   describes the destination: Nd = n_homes homes in E = max(n_groups, 1) groups of Nb = Nd / E homes.  The
+   source holds `copies` = C copies of it, copy-major -- copy c in columns [c * Nd, (c + 1) * Nd), the layout
+   dragg_mpc_replicate writes with G = C -- so its vals are [DRAGG_NVAL][C * Nd], its fc [C * Nd][DRAGG_NFC][H]
+   and its per-home outputs C * Nd wide.  `choice` is a device int32 [E]: group e of the destination
+   receives, from copy choice[e], the columns of its Nb homes -- every row of vals, each home's fc block, and
+   every member of dragg_mpc_out that is non-NULL in BOTH src_out and dst_out (status, iters, obj, relax_obj,
+   int_path, hist; cycles is ignored; either struct may be NULL: the hash arrays alone).  A choice outside
+   [0, C) leaves every column of group e untouched -- no byte of it is written: idle or parked episodes and
+   "no valid candidate" pass through.  Bit for bit (NaN payloads included: NaN = field absent); src_* is
+   only read.  One kernel; a block works on one group, so the choice is read once per block.  n_homes == 0:
+   a no-op.  DRAGG_E_ARG: copies < 1, n_homes % E != 0, E > 65535, a NULL choice or NULL hash pointers. */
+int dragg_mpc_adopt(const dragg_mpc_dims* dst_dims, int32_t copies, const int32_t* choice,
+                    const dragg_mpc_hash* src_hash, const dragg_mpc_out* src_out,
+                    dragg_mpc_hash* dst_hash, dragg_mpc_out* dst_out, void* stream);
+
+/* The choice for dragg_mpc_adopt, made on the device (since v10, additive): for each group e of `dst_dims`
+   the copy c that minimises |sums[c * E + e][0] - target[e]| (sums: dragg_mpc_aggregate_groups' rows of the
+   C * E-group source, [C * E][3]; target [E]); ties go to the smaller |prices[c * E + e][0]| (prices
+   [C * E][n_rp], the source's reward-price rows), then to the smaller c.  The doubles are compared as they
+   are, no tolerance.  A copy whose load is NaN is never chosen; choice[e] = -1 if none is valid. */
+int dragg_mpc_select_groups(const dragg_mpc_dims* dst_dims, int32_t copies, const double* sums,
+                            const double* target, const double* prices, int32_t n_rp, int32_t* choice,
+                            void* stream);
+
 /* collect_data's sums of every group of a grouped batch (since v10): out[G][3], row g exactly as
    dragg_mpc_aggregate on a batch holding group g's Nb homes (the same lanes and reduction order:
    bit-identical); a NaN makes only its own group's sum NaN.  G <= 1: one row, dragg_mpc_aggregate's.
