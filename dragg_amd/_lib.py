@@ -87,6 +87,19 @@ class Episodes(ctypes.Structure):
     _fields_ = [("seed", c_dp), ("start_index", c_dp), ("timestep", c_dp)]
 
 
+class Env(ctypes.Structure):
+    """dragg_mpc_env: a vector environment's device-resident state and history stores (dragg_mpc_env_file,
+    dragg_mpc_env_reset)."""
+    _fields_ = [("num_timesteps", ctypes.c_int32), ("prev_timesteps", ctypes.c_int32),
+                ("max_poss_load", ctypes.c_double), ("start_load", ctypes.c_double), ("ran", c_dp), ("clock", c_dp),
+                ("max_load", c_dp), ("min_load", c_dp), ("tracked", c_dp), ("obs", c_dp), ("sums", c_dp),
+                ("status_hist", c_dp), ("path_hist", c_dp), ("hist", c_dp), ("agg_hist", c_dp)]
+
+
+ENV_PREV_MAX = 128             # DRAGG_ENV_PREV_MAX: the tracked loads the device setpoint takes
+OBS_KEYS = ("agg_load", "forecast_load", "agg_cost", "agg_setpoint", "timestep")    # rows of dragg_mpc_env.obs
+
+
 class Lag(ctypes.Structure):
     _fields_ = [("clock", c_dp), ("skipped", c_dp), ("narrow", c_dp), ("side_workspace", c_dp)]
 
@@ -135,7 +148,8 @@ EXPORTS = ["dragg_mpc_abi_version", "dragg_mpc_strerror", "dragg_mpc_lds_bytes",
            "dragg_mpc_lag_reset", "dragg_mpc_step_main", "dragg_mpc_step_side", "dragg_mpc_aggregate_rows",
            "dragg_mpc_side_workspace_bytes", "dragg_mpc_side_grid", "dragg_mpc_source_hash",
            "dragg_mpc_replicate", "dragg_mpc_aggregate_groups", "dragg_mpc_step_episodes",
-           "dragg_mpc_season_noise_episodes", "dragg_mpc_adopt", "dragg_mpc_select_groups"]
+           "dragg_mpc_season_noise_episodes", "dragg_mpc_adopt", "dragg_mpc_select_groups", "dragg_mpc_env_file",
+           "dragg_mpc_env_reset"]
 
 _LIB = None
 
@@ -205,6 +219,8 @@ def load(path=LIB_PATH):
                                     ctypes.POINTER(Hash), ctypes.POINTER(Out), c_dp]
     lib.dragg_mpc_select_groups.argtypes = [ctypes.POINTER(Dims), ctypes.c_int32, c_dp, c_dp, c_dp, ctypes.c_int32,
                                             c_dp, c_dp]
+    lib.dragg_mpc_env_file.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Env), ctypes.POINTER(Out), c_dp]
+    lib.dragg_mpc_env_reset.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Env), c_dp, ctypes.POINTER(Hash), c_dp]
     if lib.dragg_mpc_abi_version() != ABI_VERSION:
         raise DraggError("ABI version mismatch between dragg_amd and libdragg_mi355x.so")
     if not os.environ.get("DRAGG_LIB"):

@@ -5134,6 +5134,137 @@ __global__ void select_groups_kernel(int E, int C, const double* sums, const dou
     choice[e] = best;
 }
 
+// The device-resident vector environment (dragg_mpc_env_file, dragg_mpc_env_reset): what the host does around
+// a step of E episodes, as one launch each, in adopt_kernel's shape -- grid (chunks, G), block (x, g) works on
+// group g alone, its key (the timestep the group ran with / its mask byte) read once per block through
+// readfirstlane, so an idle group's blocks return before any access.  Every array is a segment of `rows` rows;
+// group g's part of a row is `group_bytes` bytes at byte g * group_bytes of the row (Nb columns of 4 or 8 bytes;
+// a home's fc block; the 3 sums).  A unit is the widest of 16 / 8 / 4 bytes that divides every base, group_bytes
+// and every stride.  Lanes on consecutive units; the bits move through integer registers.  No LDS, no atomics.
+constexpr int ENV_NSEG = 6;
+struct EnvSeg {
+    const char* src;                    // file: the step's row(s); reset: unused
+    char* dst;
+    long long src_stride, dst_stride;   // bytes between rows
+    long long t_stride;                 // file: bytes between the timesteps of the store
+    long long group_bytes;
+    long long row_units;                // units of one group's part of a row
+    long long end;                      // units of this and every earlier segment, per group
+    unsigned long long fill;            // reset: the 8 bytes stored (NaN as torch.full stores it, or 0)
+    int unit;                           // bytes: 16, 8 or 4
+    int rows;
+};
+struct EnvArgs {
+    EnvSeg seg[ENV_NSEG];
+    int nseg;
+    int G, T, P;
+    double fresh_load;                  // 0.5 * max_poss_load: every tracked load of a fresh episode
+    double start_load;
+    const int32_t* ran;                 // file
+    const unsigned char* mask;          // reset
+    const double* sums;                 // file: [G][3]
+    int32_t* clock;
+    double *max_load, *min_load, *tracked, *obs;
+};
+
+// rl.setpoint_update (Aggregator.gen_setpoint's rule) for one episode, by one lane, bit for bit: the tracked
+// loads start over (`fresh`: timestep < 2) or the oldest makes room for `load`; their average is numpy's
+// (np.average of P doubles = pairwise_sum / P: below 8 elements a left-to-right sum from 0.0; from 8 to 128
+// eight accumulators over the whole blocks of 8, combined as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)),
+// then the rest left to right); then the max / min rule.  Each block of 8 is loaded before it is stored (the
+// shift reads element i + 1 for element i) and so that the loads of a block are in flight together.
+DEV void env_setpoint(const EnvArgs& a, int g, int timestep, double load, double forecast, double cost, bool fresh) {
+#pragma clang fp contract(off)   // bit-identical to numpy's sum and division
+    const int P = a.P;
+    double* tr = a.tracked + (size_t)g * P;
+    double mx = fresh ? -__builtin_inf() : a.max_load[g], mn = fresh ? __builtin_inf() : a.min_load[g];
+    auto next = [&](int i) { return fresh ? a.fresh_load : i < P - 1 ? tr[i + 1] : load; };
+    double res = 0.0;
+    int i = 0;
+    if (P >= 8) {
+        double r[8] = {};
+        const int n8 = P - P % 8;
+        for (; i < n8; i += 8) {
+            double v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = next(i + j);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                tr[i + j] = v[j];
+                r[j] = i == 0 ? v[j] : r[j] + v[j];
+            }
+        }
+        res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    }
+    for (; i < P; ++i) {
+        const double v = next(i);
+        tr[i] = v;
+        res += v;
+    }
+    const double avg = res / (double)P;
+    const bool day = timestep % 24 == 0;
+    if (load > mx || day) mx = load;
+    if (load < mn || day) mn = load;
+    a.max_load[g] = mx;
+    a.min_load[g] = mn;
+    a.clock[g] = timestep;
+    const size_t G = (size_t)a.G;
+    a.obs[g] = load;
+    a.obs[G + g] = forecast;
+    a.obs[2 * G + g] = cost;
+    a.obs[3 * G + g] = avg;
+    a.obs[4 * G + g] = (double)timestep;
+}
+
+template <typename T>
+DEV void env_copy(const EnvSeg& s, long long u, long long g, long long t) {
+    const long long r = s.rows == 1 ? 0 : u / s.row_units, i = u - r * s.row_units;
+    const T* p = reinterpret_cast<const T*>(s.src + r * s.src_stride + g * s.group_bytes) + i;
+    T* q = reinterpret_cast<T*>(s.dst + t * s.t_stride + r * s.dst_stride + g * s.group_bytes) + i;
+    *q = *p;
+}
+__global__ __launch_bounds__(REP_NT) void env_file_kernel(EnvArgs a) {
+    const int g = (int)blockIdx.y;
+    const int t = __builtin_amdgcn_readfirstlane(a.ran[g]);
+    if (t < 0 || t >= a.T) return;
+    const long long n = a.nseg ? a.seg[a.nseg - 1].end : 0;
+    for (long long x = (long long)blockIdx.x * REP_NT + threadIdx.x; x < n; x += (long long)gridDim.x * REP_NT) {
+        int k = 0;
+        while (x >= a.seg[k].end) ++k;
+        const EnvSeg& s = a.seg[k];
+        const long long u = x - (k ? a.seg[k - 1].end : 0);
+        if (s.unit == 16) env_copy<uint4>(s, u, g, t);
+        else if (s.unit == 8) env_copy<unsigned long long>(s, u, g, t);
+        else env_copy<unsigned>(s, u, g, t);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const double* s3 = a.sums + (size_t)g * 3;
+        env_setpoint(a, g, t + 1, s3[0], s3[1], s3[2], t + 1 < 2);
+    }
+}
+
+template <typename T>
+DEV void env_fill(const EnvSeg& s, long long u, long long g, T v) {
+    const long long r = s.rows == 1 ? 0 : u / s.row_units, i = u - r * s.row_units;
+    reinterpret_cast<T*>(s.dst + r * s.dst_stride + g * s.group_bytes)[i] = v;
+}
+__global__ __launch_bounds__(REP_NT) void env_reset_kernel(EnvArgs a) {
+    const int g = (int)blockIdx.y;
+    if (!__builtin_amdgcn_readfirstlane((int)a.mask[g])) return;
+    const long long n = a.nseg ? a.seg[a.nseg - 1].end : 0;
+    for (long long x = (long long)blockIdx.x * REP_NT + threadIdx.x; x < n; x += (long long)gridDim.x * REP_NT) {
+        int k = 0;
+        while (x >= a.seg[k].end) ++k;
+        const EnvSeg& s = a.seg[k];
+        const long long u = x - (k ? a.seg[k - 1].end : 0);
+        const unsigned lo = (unsigned)s.fill, hi = (unsigned)(s.fill >> 32);
+        if (s.unit == 16) env_fill<uint4>(s, u, g, uint4{lo, hi, lo, hi});
+        else if (s.unit == 8) env_fill<unsigned long long>(s, u, g, s.fill);
+        else env_fill<unsigned>(s, u, g, lo);        // (4-byte units: the int32 stores, filled with 0)
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) env_setpoint(a, g, 0, a.start_load, a.start_load, 0.0, true);
+}
+
 // (nb: the base homes of a grouped batch, N otherwise.  Home r of group g = r / nb draws the stream of
 // (ep.seed[g] -- NULL: seed --, its base home, ep.timestep[g] -- NULL: t); the columns of a group whose own
 // timestep is negative are left as they are)
@@ -5755,6 +5886,97 @@ int dragg_mpc_aggregate_groups(const dragg_mpc_dims* dims, const dragg_mpc_hash*
     hipLaunchKernelGGL(aggregate_groups_kernel, dim3(G), dim3(AGG_NT), 0, (hipStream_t)stream, hash->vals,
                        dims->n_homes, dims->n_homes / G, out);
     return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+}
+
+// the checks and members both environment entry points share; G < 0: DRAGG_E_ARG
+static int env_args(const dragg_mpc_dims* dims, const dragg_mpc_env* env, EnvArgs& a) {
+    if (!dims || !env || dims->n_homes < 0) return DRAGG_E_ARG;
+    const int G = group_count(dims);
+    if (G < 0 || G > 65535) return DRAGG_E_ARG;        // (a grid row per group)
+    if (env->prev_timesteps < 1 || env->prev_timesteps > DRAGG_ENV_PREV_MAX || env->num_timesteps < 1) return DRAGG_E_ARG;
+    if (!env->clock || !env->obs || !env->max_load || !env->min_load || !env->tracked) return DRAGG_E_ARG;
+    a.G = G;
+    a.T = env->num_timesteps;
+    a.P = env->prev_timesteps;
+    a.fresh_load = 0.5 * env->max_poss_load;
+    a.start_load = env->start_load;
+    a.clock = env->clock;
+    a.max_load = env->max_load;
+    a.min_load = env->min_load;
+    a.tracked = env->tracked;
+    a.obs = env->obs;
+    return G;
+}
+
+// one segment more: `rows` rows of which group g owns group_bytes bytes at byte g * group_bytes (row strides
+// G * group_bytes; the store's timesteps rows * that apart).  false: an address not aligned to its elements
+static bool env_seg(EnvArgs& a, const void* src, void* dst, long long group_bytes, int rows, long long elem,
+                    unsigned long long fill) {
+    const long long stride = a.G * group_bytes;
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) |
+                           (uintptr_t)group_bytes | (uintptr_t)stride;
+    if (bits % elem != 0) return false;
+    const int unit = bits % 16 == 0 ? 16 : bits % 8 == 0 ? 8 : 4;
+    EnvSeg& s = a.seg[a.nseg];
+    s = EnvSeg{static_cast<const char*>(src), static_cast<char*>(dst), stride, stride, rows * stride, group_bytes,
+               group_bytes / unit, 0, fill, unit, rows};
+    s.end = (a.nseg ? a.seg[a.nseg - 1].end : 0) + rows * s.row_units;
+    ++a.nseg;
+    return true;
+}
+
+static int env_launch(void (*kernel)(EnvArgs), const EnvArgs& a, void* stream) {
+    const long long units = a.nseg ? a.seg[a.nseg - 1].end : 0;
+    const long long blocks = max(1LL, (units + REP_NT - 1) / REP_NT);
+    const long long cap = max(1LL, (long long)REP_BLOCKS_MAX / a.G);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)min(blocks, cap), (unsigned)a.G), dim3(REP_NT), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+}
+
+int dragg_mpc_env_file(const dragg_mpc_dims* dims, const dragg_mpc_env* env, const dragg_mpc_out* out, void* stream) {
+    EnvArgs a{};
+    const int G = env_args(dims, env, a);
+    if (G < 0) return DRAGG_E_ARG;
+    if (!env->ran || !env->sums || static_cast<const void*>(env->ran) == static_cast<const void*>(env->clock))
+        return DRAGG_E_ARG;
+    // a store and its source come together
+    const int32_t* status = out ? out->status : nullptr;
+    const int32_t* path = out ? out->int_path : nullptr;
+    const double* row = out ? out->hist : nullptr;
+    if (!status != !env->status_hist || !path != !env->path_hist || !row != !env->hist) return DRAGG_E_ARG;
+    if (dims->n_homes == 0) return DRAGG_OK;
+    a.ran = env->ran;
+    a.sums = env->sums;
+    const long long Nb = dims->n_homes / G;
+    bool ok = true;
+    if (row) ok = ok && env_seg(a, row, env->hist, Nb * 8, DRAGG_NVAL, 8, 0);
+    if (status) ok = ok && env_seg(a, status, env->status_hist, Nb * 4, 1, 4, 0);
+    if (path) ok = ok && env_seg(a, path, env->path_hist, Nb * 4, 1, 4, 0);
+    if (env->agg_hist) ok = ok && env_seg(a, env->sums, env->agg_hist, 3 * 8, 1, 8, 0);
+    if (!ok) return DRAGG_E_ARG;
+    return env_launch(env_file_kernel, a, stream);
+}
+
+int dragg_mpc_env_reset(const dragg_mpc_dims* dims, const dragg_mpc_env* env, const uint8_t* mask,
+                        dragg_mpc_hash* hash, void* stream) {
+    EnvArgs a{};
+    const int G = env_args(dims, env, a);
+    if (G < 0 || !mask || !hash || dims->horizon < 1) return DRAGG_E_ARG;
+    if (dims->n_homes == 0) return DRAGG_OK;
+    if (!hash->vals || !hash->fc) return DRAGG_E_ARG;
+    a.mask = mask;
+    const long long Nb = dims->n_homes / G;
+    const int T = env->num_timesteps;
+    const unsigned long long nan = 0x7FF8000000000000ull;       // the quiet NaN torch.full(nan) and numpy store
+    bool ok = true;
+    if (env->hist) ok = ok && env_seg(a, nullptr, env->hist, Nb * 8, T * DRAGG_NVAL, 8, nan);
+    ok = ok && env_seg(a, nullptr, hash->fc, Nb * DRAGG_NFC * dims->horizon * 8, 1, 8, nan);
+    ok = ok && env_seg(a, nullptr, hash->vals, Nb * 8, DRAGG_NVAL, 8, nan);
+    if (env->status_hist) ok = ok && env_seg(a, nullptr, env->status_hist, Nb * 4, T, 4, 0);
+    if (env->path_hist) ok = ok && env_seg(a, nullptr, env->path_hist, Nb * 4, T, 4, 0);
+    if (env->agg_hist) ok = ok && env_seg(a, nullptr, env->agg_hist, 3 * 8, T, 8, 0);
+    if (!ok) return DRAGG_E_ARG;
+    return env_launch(env_reset_kernel, a, stream);
 }
 
 }  // extern "C"

@@ -487,6 +487,38 @@ class MPCBatch:
             self._call(self.lib.dragg_mpc_aggregate_groups, self._hash(), L.ptr(self.agg_groups), stream=stream)
             return self.agg_groups
 
+    # ------------------------------------------------------------------ device-resident environment
+    def _env(self, st, ran=None, sums=None):
+        """The dragg_mpc_env struct of an environment state (`dragg_amd.vector.EnvState`: scalars, the state
+        tensors and the history stores, None where a store is not kept)."""
+        return L.Env(num_timesteps=int(st.num_timesteps), prev_timesteps=int(st.prev_timesteps),
+                     max_poss_load=float(st.max_poss_load), start_load=float(st.start_load), ran=L.ptr(ran),
+                     clock=L.ptr(st.clock), max_load=L.ptr(st.max_load), min_load=L.ptr(st.min_load),
+                     tracked=L.ptr(st.tracked), obs=L.ptr(st.obs), sums=L.ptr(sums),
+                     status_hist=L.ptr(st.status_hist), path_hist=L.ptr(st.path_hist), hist=L.ptr(st.hist),
+                     agg_hist=L.ptr(st.agg_hist))
+
+    def env_file(self, st, ran, sums, hist=None, stream=None):
+        """After a step that ran with the timesteps `ran` (device int32 [G]; negative: idle): file the step's
+        status, int_path and history row (`hist` [NVAL][N]) at row ran[g] of the stores of `st`, the sums
+        (`sums` [G][3], `aggregate_groups`') into its agg_hist, advance its clocks and update the environment
+        state and observations -- one kernel (dragg_mpc_env_file).  No synchronisation."""
+        with torch.cuda.device(self.device):
+            out = L.Out(status=L.ptr(self.status), hist=L.ptr(hist if st.hist is not None else None),
+                        int_path=L.ptr(self.int_path if st.path_hist is not None else None))
+            self._call(self.lib.dragg_mpc_env_file, self._env(st, ran, sums), out, stream=stream)
+            self._keep = (ran, sums, hist)
+
+    def env_reset(self, st, mask, stream=None):
+        """Start the masked groups (`mask`: device bool [G]) over: their columns of vals and fc NaN, their
+        columns of every store of `st` cleared, clock 0, the environment state of a fresh episode -- one
+        kernel (dragg_mpc_env_reset) that touches the masked groups' columns only.  No synchronisation."""
+        with torch.cuda.device(self.device):
+            self.drain(stream)
+            L.check(self.lib.dragg_mpc_env_reset(self.dims, self._env(st), L.ptr(mask), self._hash(),
+                                                 L.stream_ptr(stream, self.device)))
+            self._keep = (mask,)
+
     def season_noise(self, t, stream=None):
         with torch.cuda.device(self.device):
             out = torch.empty((self.H, self.N), dtype=torch.float64, device=self.device)

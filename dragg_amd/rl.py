@@ -7,7 +7,9 @@ aggregate load, its forecast, the setpoint and candidate-price rollouts -- comes
 device-resident solves; `rl_sweep` solves G candidate prices in one grouped launch (`SweepAgent`).
 `VectorEnv` (`Aggregator.rl_vector`) steps E independent episodes of the community as one batch, each
 with its own seed, start index, clock and price, for policies that learn over many episodes
-(`SetpointAgent.train_vector`).
+(`SetpointAgent.train_vector`).  `DeviceVectorEnv` (`Aggregator.rl_vector(E, device_env=True)`) is the same
+environment with its state, observations, done flags and choices kept on the device, for policies that are
+device code themselves (`SetpointAgent.act_device`, `SweepAgent.act_device`): no step or reset synchronises.
 
 The reference's learning agent (`dragg/agent.py`, an abstract actor-critic whose
 `calc_state` / `reward` are left to a subclass and which no driver of v1 calls) is out of
@@ -123,6 +125,46 @@ class SetpointAgent:
         """Observations -> reward prices [E] for `VectorEnv.step`."""
         return self.train_vector(env_obs) / self.scale
 
+    def train_device(self, env_obs, history=True):
+        """`train_vector` on device tensors (the observations of a `DeviceVectorEnv`), as float64 elementwise
+        torch ops -- every arithmetic step an op of its own, so that nothing is contracted and the actions
+        equal `train_vector`'s bit for bit.  The PI state (`integral_d`) stays on the device; history=True
+        appends the errors and actions to `history_device` as device tensors.  -> actions, device [E]."""
+        import torch
+        f, s = env_obs["forecast_load"], env_obs["agg_setpoint"]
+        sp = torch.where(s != 0, s, torch.ones_like(s))
+        e = f - sp
+        e = e / sp
+        if getattr(self, "integral_d", None) is None or self.integral_d.shape != e.shape \
+                or self.integral_d.device != e.device:
+            self.integral_d = torch.zeros_like(e)
+        if self.ki:
+            self.integral_d = torch.clamp(self.integral_d + e, self.lo / self.ki, self.hi / self.ki)
+        p = self.kp * e
+        i = self.ki * self.integral_d
+        a = torch.clamp(p + i, self.lo, self.hi)
+        if history:
+            if getattr(self, "history_device", None) is None:
+                self.history_device = {"error": [], "action": []}
+            self.history_device["error"].append(e)
+            self.history_device["action"].append(a)
+        return a
+
+    def reset_device(self, mask=None):
+        """Clear the device PI state of the masked episodes (`mask`: a device bool [E]; default: all)."""
+        import torch
+        if getattr(self, "integral_d", None) is not None:
+            zero = torch.zeros_like(self.integral_d)
+            self.integral_d = zero if mask is None else torch.where(mask, zero, self.integral_d)
+
+    def act_device(self, env_obs, history=True):
+        """Device observations -> reward prices, device [E], for `DeviceVectorEnv.step`.  (The divisor is a
+        tensor: torch divides a device tensor by a Python scalar as a multiplication by its reciprocal, which
+        is not `act_vector`'s division in the last bit.)"""
+        import torch
+        a = self.train_device(env_obs, history)
+        return a / torch.full_like(a, self.scale)
+
 
 class VectorEnv:
     """E episodes of one community as a vector environment for reward-price policies, on a
@@ -225,6 +267,64 @@ class VectorEnv:
         return self.observations(), self.done()
 
 
+class DeviceVectorEnv:
+    """`VectorEnv` with everything kept on the device: the same constructor arguments and methods, the same
+    numbers bit for bit, but the work after a step's solve is one kernel (dragg_mpc_env_file: the history rows,
+    the clocks, the setpoint rule and the observations) and a reset is one kernel over the restarted episodes'
+    columns alone (dragg_mpc_env_reset).  No method synchronises with the host.
+
+    Everything returned is a device tensor: `observations()` is a dict of [E] float64 VIEWS into one buffer
+    (`timestep` too: exact in a double) -- a later step or reset overwrites them, so clone what must be kept;
+    `done()` is a device bool [E]; `choice` (after `step_swept`) a device int32 [E].  `reset` and `park` take
+    device masks (`env.reset(env.done())`), and `reset` takes `seeds` / `start_indices` as device tensors [E],
+    used for the masked episodes without a host check: a start index outside the environment window leaves that
+    episode idle.  Host lists are taken and checked as in `VectorEnv`.  `agg.rl.prev_timesteps` must lie in
+    1..128."""
+
+    def __init__(self, vector_aggregator, config, max_poss_load=None, n_homes=None):
+        from . import inputs as I
+        self.va = va = vector_aggregator
+        self.config = config
+        self.E, self.T = va.E, va.num_timesteps
+        self.prev_timesteps = config["agg"]["rl"]["prev_timesteps"]
+        self.max_poss_load = (sum(I.max_load(h) for h in va.homes) if max_poss_load is None else max_poss_load)
+        self.n_homes = va.Nb if n_homes is None else int(n_homes)
+        self.state = va.env_state(self.prev_timesteps, self.max_poss_load, 3 * self.n_homes)
+        self.choice = None
+
+    def observations(self):
+        from ._lib import OBS_KEYS
+        return {k: self.state.obs[i] for i, k in enumerate(OBS_KEYS)}
+
+    def reset(self, mask=None, seeds=None, start_indices=None):
+        self.va.reset_env(self.state, mask, seeds=seeds, start_indices=start_indices)
+        return self.observations()
+
+    def park(self, mask):
+        self.va.park(mask)
+
+    def resume(self, mask):
+        self.va.resume(mask)
+
+    def done(self):
+        return self.va.done()
+
+    def step(self, actions):
+        """-> (observations, done [E]), as `VectorEnv.step`."""
+        self.va.step_env(self.state, actions)
+        return self.observations(), self.done()
+
+    def step_swept(self, candidates):
+        """-> (observations, done [E]), as `VectorEnv.step_swept`; the setpoints go to `select` from the device."""
+        import torch
+        va = self.va
+        sums = va.sweep(candidates)
+        choice = va.select(sums, self.state.obs[3], candidates)
+        va.commit_env(self.state, choice)
+        self.choice = torch.where(va.adopted, choice, torch.full_like(choice, -1))
+        return self.observations(), self.done()
+
+
 class SweepAgent:
     """Evaluates the price-response curve instead of guessing it: `n_candidates` actions evenly
     spaced over `rl.utility.action_space` (divided by `action_scale`: $/kWh) are all solved ahead
@@ -274,6 +374,17 @@ class SweepAgent:
         the same `candidates()`)."""
         E = len(np.asarray(env_obs["agg_setpoint"]).reshape(-1))
         return np.tile(self.candidates() / self.scale, (E, 1))
+
+    def act_device(self, env_obs):
+        """`act_vector` for a `DeviceVectorEnv`: the tiled candidates as a device tensor [E][C] (built once per
+        shape and device)."""
+        import torch
+        s = env_obs["agg_setpoint"]
+        key = (int(s.numel()), s.device)
+        if getattr(self, "_tiled", None) is None or self._tiled[0] != key:
+            self._tiled = (key, torch.as_tensor(np.tile(self.candidates() / self.scale, (key[0], 1)),
+                                                dtype=torch.float64).to(s.device))
+        return self._tiled[1]
 
 
 def agent_policy(aggregator):

@@ -214,11 +214,12 @@ class Aggregator:
             self.config["agg"]["rl"]["prev_timesteps"] if fresh else None)
         return self.avg_load
 
-    def rl_vector(self, episodes, seeds=None, start_indices=None):
+    def rl_vector(self, episodes, seeds=None, start_indices=None, device_env=False):
         """A vector environment of `episodes` independent runs of the loaded community (`get_homes`), all
         stepped as one grouped batch (dragg_amd.vector.VectorAggregator, rl.VectorEnv): default seeds
-        `simulation.random_seed + e`, default start indices the config's own.  One rank only."""
-        from .rl import VectorEnv
+        `simulation.random_seed + e`, default start indices the config's own.  device_env=True: an
+        `rl.DeviceVectorEnv` (observations, done flags and choices stay on the device).  One rank only."""
+        from .rl import DeviceVectorEnv, VectorEnv
         from .vector import VectorAggregator
         if self.world > 1:
             raise ValueError("rl_vector runs on one rank: episodes are not sharded over ranks")
@@ -232,8 +233,8 @@ class Aggregator:
                               [self.start_hour_index] * E if start_indices is None else start_indices,
                               self.num_timesteps, int_mode=self.int_mode, device=self.device,
                               **({"batch_cls": self.batch_cls} if self.batch_cls else {}))
-        return VectorEnv(va, self.config, max_poss_load=sum(I.max_load(h) for h in self.all_homes),
-                         n_homes=len(self.all_homes))
+        return (DeviceVectorEnv if device_env else VectorEnv)(
+            va, self.config, max_poss_load=sum(I.max_load(h) for h in self.all_homes), n_homes=len(self.all_homes))
 
     # aggregator.py:664-675: the reward price goes to every rank's solver (RCCL broadcast from
     # rank 0) instead of the redis 'reward_price' list

@@ -13,6 +13,12 @@ The seeds, start indices and clocks live on the device and the kernels read them
 park or a resume never synchronises with the host.  Only the accessors that hand rows to the host
 (`episode_history`, `episode_status`, `episode_paths`, `approx_counts`, `check_errors`, `clocks_host`) do.
 
+`step_env`, `commit_env` and `reset_env` are `step`, `commit` and `reset` for a device-resident environment
+(`rl.DeviceVectorEnv`): the same solve, then ONE kernel that files the rows, advances the clocks and keeps the
+environment's setpoint state and observations (dragg_mpc_env_file), and one kernel that starts the masked
+episodes over by writing their columns alone (dragg_mpc_env_reset).  `env_file_reference` and
+`env_reset_reference` restate the two kernels on numpy arrays for the tests.
+
 One rank only: sharding episodes over ranks is not built.
 """
 import numpy as np
@@ -26,6 +32,98 @@ def _seed_i64(s):
     """A uint64 seed as the int64 with the same bits (the tensors are int64)."""
     s = int(s) & (2 ** 64 - 1)
     return s - 2 ** 64 if s >= 2 ** 63 else s
+
+
+class EnvState:
+    """What a device-resident environment keeps per episode beside the aggregator's own arrays (the members of
+    dragg_mpc_env, include/dragg_mi355x.h): the setpoint rule's tracked loads [E][P] (oldest first), max_load
+    and min_load [E], and the observations [5][E] (rows: L.OBS_KEYS).  The clocks and the history stores are
+    the aggregator's, looked up when a call is made (its host-driven methods rebind `clocks`)."""
+
+    def __init__(self, va, prev_timesteps, max_poss_load, start_load):
+        P = int(prev_timesteps)
+        if not 1 <= P <= L.ENV_PREV_MAX:
+            raise ValueError(f"prev_timesteps must lie in 1..{L.ENV_PREV_MAX} for a device-resident environment, "
+                             f"not {prev_timesteps!r}")
+        self.va = va
+        self.num_timesteps, self.prev_timesteps = va.num_timesteps, P
+        self.max_poss_load, self.start_load = float(max_poss_load), float(start_load)
+        dev, E = va.device, va.E
+        self.tracked = torch.zeros((E, P), dtype=torch.float64, device=dev)
+        self.max_load = torch.full((E,), -float("inf"), dtype=torch.float64, device=dev)
+        self.min_load = torch.full((E,), float("inf"), dtype=torch.float64, device=dev)
+        self.obs = torch.zeros((len(L.OBS_KEYS), E), dtype=torch.float64, device=dev)
+
+    clock = property(lambda self: self.va.clocks)
+    status_hist = property(lambda self: self.va.status_hist)
+    path_hist = property(lambda self: self.va.path_hist)
+    hist = property(lambda self: self.va.hist)
+    agg_hist = property(lambda self: self.va.agg_hist)
+
+    def host(self):
+        """The arrays as numpy, for the restatements below (CPU tensors: views that share their memory)."""
+        out = {k: getattr(self, k) for k in ("num_timesteps", "prev_timesteps", "max_poss_load", "start_load")}
+        for k in ("clock", "tracked", "max_load", "min_load", "obs", "status_hist", "path_hist", "hist", "agg_hist"):
+            t = getattr(self, k)
+            out[k] = None if t is None else t.cpu().numpy()
+        return out
+
+
+def env_file_reference(env, ran, sums, status=None, int_path=None, row=None):
+    """dragg_mpc_env_file restated on numpy arrays, in place (the spec its tests share, and what a stand-in
+    batch serves `env_file` with -- not a solver fallback).  `env`: `EnvState.host()`'s dict; `ran` [G], `sums`
+    [G][3], `status` / `int_path` [N], `row` [NVAL][N].  Group g with 0 <= ran[g] < T: its Nb columns of the
+    sources filed at row ran[g] of the stores, clock ran[g] + 1, then `VectorEnv.step`'s bookkeeping with
+    `rl.setpoint_update` itself; any other group: nothing written."""
+    from .rl import setpoint_update
+    G = len(ran)
+    for g in range(G):
+        t = int(ran[g])
+        if t < 0 or t >= env["num_timesteps"]:
+            continue
+        for store, src in ((env["status_hist"], status), (env["path_hist"], int_path), (env["hist"], row)):
+            if store is not None and src is not None:
+                Nb = store.shape[-1] // G
+                store[t, ..., g * Nb:(g + 1) * Nb] = src[..., g * Nb:(g + 1) * Nb]
+        if env["agg_hist"] is not None:
+            env["agg_hist"][t, g] = sums[g]
+        ts = t + 1
+        env["clock"][g] = ts
+        load = float(sums[g][0])
+        tracked, mx, mn, avg = setpoint_update((env["tracked"][g].tolist(), float(env["max_load"][g]),
+                                                float(env["min_load"][g])), ts, load, env["max_poss_load"],
+                                               env["prev_timesteps"])
+        env["tracked"][g] = tracked
+        env["max_load"][g], env["min_load"][g] = mx, mn
+        env["obs"][:, g] = (load, sums[g][1], sums[g][2], avg, ts)
+
+
+def env_reset_reference(env, mask, vals, fc):
+    """dragg_mpc_env_reset restated on numpy arrays, in place: for each masked group, its columns of `vals`
+    ([NVAL][N]) and its homes' blocks of `fc` ([N][NFC][H]) NaN, its columns of every store cleared, clock 0,
+    and the state `VectorEnv.reset` leaves (through `rl.setpoint_update` itself)."""
+    from .rl import setpoint_update
+    G = len(mask)
+    Nb = vals.shape[-1] // G
+    for g in range(G):
+        if not mask[g]:
+            continue
+        cols = slice(g * Nb, (g + 1) * Nb)
+        vals[:, cols] = np.nan
+        fc[cols] = np.nan
+        if env["hist"] is not None:
+            env["hist"][..., cols] = np.nan
+        env["status_hist"][:, cols] = 0
+        if env["path_hist"] is not None:
+            env["path_hist"][:, cols] = 0
+        if env["agg_hist"] is not None:
+            env["agg_hist"][:, g] = 0.0
+        env["clock"][g] = 0
+        load = env["start_load"]
+        tracked, mx, mn, avg = setpoint_update(None, 0, load, env["max_poss_load"], env["prev_timesteps"])
+        env["tracked"][g] = tracked
+        env["max_load"][g], env["min_load"][g] = mx, mn
+        env["obs"][:, g] = (load, load, 0.0, avg, 0)
 
 
 class VectorAggregator:
@@ -154,6 +252,11 @@ class VectorAggregator:
         episode e's reward-price list); the others stay idle.  -> device tensor [E][3], collect_data's
         [agg_load, forecast_load, agg_cost] per episode (an idle episode's row: its state's, i.e. its last
         step's sums, NaN before its first).  The active clocks advance on the device."""
+        return self._file(self._advance(prices, noise))
+
+    def _advance(self, prices, noise=None):
+        """The solve of `step`: the prices published, every active episode stepped at its own clock (kept in
+        `self._keep`, -1 for the others) -> the device bool [E] of the episodes that ran.  Nothing filed yet."""
         P = L.device_f64(prices, self.device)
         if P.dim() == 1:
             P = P.reshape(-1, 1)
@@ -170,7 +273,7 @@ class VectorAggregator:
             self._row.fill_(float("nan"))
         b.step_episodes(self.seeds, self.starts, eff, noise=noise, hist=self._row)
         self._keep = eff
-        return self._file(on)
+        return on
 
     def _file(self, on):
         """After a step of the episodes `on` (solved, or adopted): their sums, the step's rows filed at each
@@ -257,6 +360,11 @@ class VectorAggregator:
         adopts nothing and stays where it is.  The chosen rows become the live batch's reward price (an
         episode that adopted nothing: its candidate 0's row, which nothing reads).  -> [E][3], the episodes'
         sums as `step` returns them; `self.adopted` (device bool [E]) holds the episodes that advanced."""
+        return self._file(self._adopt(choice))
+
+    def _adopt(self, choice):
+        """The adoption of `commit` -> the device bool [E] of the episodes that adopted a step (also
+        `self.adopted`).  Nothing filed yet."""
         h = self._hold
         if h is None or h["gen"] != self._gen:
             raise ValueError("commit: no sweep of the live state is held (sweep first; a step or a reset voids it)")
@@ -274,7 +382,54 @@ class VectorAggregator:
             self._row.fill_(float("nan"))
         b.adopt_from(rb, ch, hist=self._row)
         self.adopted = on
-        return self._file(on)
+        return on
+
+    # ------------------------------------------------------------------ the device-resident environment's paths
+    # `step`, `commit` and `reset` again, ending in one kernel each (MPCBatch.env_file / env_reset) instead of
+    # `_file`'s gathers and scatters and `reset`'s whole-store rewrites; the kernel also keeps the environment
+    # state of an `rl.DeviceVectorEnv` (`EnvState`).  The clocks are written in place.
+    def env_state(self, prev_timesteps, max_poss_load, start_load):
+        return EnvState(self, prev_timesteps, max_poss_load, start_load)
+
+    def _env_file(self, st, on, ran=None):
+        """File the step of the episodes `on`; `ran`: the clocks they ran at, -1 for the others (a tensor of
+        its own: the kernel reads it in every block and writes the clocks)."""
+        if ran is None:
+            ran = torch.where(on, self.clocks, torch.full_like(self.clocks, -1))
+        agg = self.batch.aggregate_groups()
+        self.batch.env_file(st, ran, agg, hist=self._row)
+        return agg
+
+    def step_env(self, st, prices, noise=None):
+        """`step`, filed by dragg_mpc_env_file: the same solve, sums, rows and clocks, plus the environment
+        state `st` (`env_state`) and its observations.  -> [E][3]"""
+        on = self._advance(prices, noise)
+        return self._env_file(st, on, self._keep)
+
+    def commit_env(self, st, choice):
+        """`commit`, filed by dragg_mpc_env_file (the episodes that ran: those that adopted a step)."""
+        return self._env_file(st, self._adopt(choice))
+
+    def reset_env(self, st, mask=None, seeds=None, start_indices=None):
+        """`reset` as one kernel over the masked episodes' columns alone (dragg_mpc_env_reset), the
+        environment state `st` started over with them.  `mask` may be a device bool tensor [E] (e.g.
+        `done()`), `seeds` / `start_indices` device tensors [E]: they are taken for the masked episodes with no
+        host check and no host round trip -- an episode whose start index leaves the environment lists sits
+        idle (dragg_mpc_step_episodes).  Host lists are checked as in `reset`."""
+        m = self._mask(mask)
+        self._gen += 1
+        host = {}
+        for name, vals, dtype in (("seeds", seeds, torch.int64), ("start_indices", start_indices, torch.int32)):
+            if torch.is_tensor(vals) and vals.device == self.device:
+                if tuple(vals.shape) != (self.E,) or vals.dtype.is_floating_point:
+                    raise ValueError(f"{name}: a device int tensor [{self.E}]")
+                attr = "seeds" if name == "seeds" else "starts"
+                setattr(self, attr, torch.where(m, vals.to(dtype), getattr(self, attr)))
+            else:
+                host[name] = vals
+        self._set_keys(None if mask is None else m, host.get("seeds"), host.get("start_indices"))
+        self.parked = self.parked & ~m
+        self.batch.env_reset(st, m.contiguous())
 
     # ------------------------------------------------------------------ rows for the host
     def clocks_host(self):

@@ -405,6 +405,62 @@ int dragg_mpc_season_noise_episodes(const dragg_mpc_dims* dims, const dragg_mpc_
                                     int32_t home_offset, int32_t home_stride, int32_t timestep,
                                     double* noise_out, void* stream);
 
+/* A device-resident vector environment around dragg_mpc_step_episodes (since v10, additive): what an RL
+   driver keeps per episode -- its clock, the rows of its history, collect_data's sums and the aggregator's
+   setpoint rule (gen_setpoint, aggregator.py:677-696) -- filed and updated by one kernel after a step, and
+   started over by one kernel, with no host round trip.  All pointers are device pointers; G =
+   max(dims.n_groups, 1), Nb = n_homes / G, N = n_homes.  A history store may be NULL (it is then not kept).
+     clock     [G]     steps each group has taken
+     max_load, min_load [G], tracked [G][prev_timesteps] (oldest first): gen_setpoint's state
+     obs       [5][G]  rows agg_load, forecast_load, agg_cost, agg_setpoint, timestep (exact in a double)
+     status_hist, path_hist [T][N] int32; hist [T][DRAGG_NVAL][N]; agg_hist [T][G][3]   (T = num_timesteps) */
+#define DRAGG_ENV_PREV_MAX 128
+typedef struct dragg_mpc_env {
+    int32_t num_timesteps;      /* T >= 1: rows of the history stores                                    */
+    int32_t prev_timesteps;     /* P, 1 .. DRAGG_ENV_PREV_MAX: the tracked loads (agg.rl.prev_timesteps) */
+    double max_poss_load;       /* a fresh episode tracks P loads of half of it                          */
+    double start_load;          /* agg_load and forecast_load of a fresh episode (3 kW per home)         */
+    const int32_t* ran;         /* [G] dragg_mpc_env_file: the timesteps the step just ran with          */
+                                /* (dragg_mpc_episodes.timestep; < 0 or >= T: the group took no step)    */
+    int32_t* clock;
+    double* max_load;
+    double* min_load;
+    double* tracked;
+    double* obs;
+    const double* sums;         /* [G][3] dragg_mpc_env_file: dragg_mpc_aggregate_groups' rows           */
+    int32_t* status_hist;
+    int32_t* path_hist;
+    double* hist;
+    double* agg_hist;
+} dragg_mpc_env;
+
+/* After a step: for every group g with t = env.ran[g] in [0, T), file group g's Nb columns of out.status,
+   out.int_path and out.hist (the step's [DRAGG_NVAL][N] row) into row t of status_hist, path_hist and hist,
+   and sums[g] into agg_hist[t][g]; clock[g] = t + 1; then the environment state as the host keeps it:
+   timestep = t + 1, (agg_load, forecast_load, agg_cost) = sums[g], and gen_setpoint's rule in its order --
+   at timestep < 2 the tracked loads start over at max_poss_load / 2 and max_load / min_load at -inf / +inf,
+   later the oldest tracked load makes room for agg_load; the setpoint is their average, summed in numpy's
+   pairwise order (np.average of P <= 128 doubles) and divided by P; then agg_load replaces max_load if it is
+   greater or timestep % 24 == 0, and min_load likewise -- bit for bit the host's doubles; then the five
+   observations.  A group that took no step is not touched: no byte of its columns in any store, nor its
+   clock, tracked loads, max_load, min_load or observations (its blocks return before any access).  One
+   kernel; `ran` is only read and must not be `clock`.  A store and its source come together: out.status with
+   status_hist, out.int_path with path_hist, out.hist with hist (out may be NULL when none is kept);
+   agg_hist's source is sums.  n_homes == 0: a no-op.  DRAGG_E_ARG: a NULL env, ran, clock, sums, obs,
+   max_load, min_load or tracked; P outside 1 .. DRAGG_ENV_PREV_MAX; T < 1; n_homes % G != 0; G > 65535; a
+   store without its source or a source without its store; ran == clock. */
+int dragg_mpc_env_file(const dragg_mpc_dims* dims, const dragg_mpc_env* env, const dragg_mpc_out* out,
+                       void* stream);
+
+/* Start the groups g with mask[g] != 0 (device bytes [G]) over: their columns of hash.vals and their homes'
+   blocks of hash.fc NaN (0x7ff8000000000000: field absent, the state of a new batch), their columns of every
+   row of the stores cleared (hist NaN; status_hist, path_hist and agg_hist 0), clock 0, and the environment
+   state of a fresh episode: timestep 0, agg_load = forecast_load = start_load, agg_cost 0, the setpoint rule
+   applied to fresh tracked loads.  Only the masked groups' columns are written: an unmasked group keeps
+   every byte.  One kernel; env.ran and env.sums are not read.  DRAGG_E_ARG as above, or a NULL mask or hash. */
+int dragg_mpc_env_reset(const dragg_mpc_dims* dims, const dragg_mpc_env* env, const uint8_t* mask,
+                        dragg_mpc_hash* hash, void* stream);
+
 /* Lag mode (since v8): run_rbo_mpc's timestep loop (aggregator.py:757-778) has no feedback between
    homes, so a home whose chain needs the slow exact step-function DP need not hold up the others.
    A step is split into two passes the caller puts on two streams:

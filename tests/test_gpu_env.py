@@ -1,0 +1,299 @@
+"""The device-resident vector environment on the GPU: dragg_mpc_env_file and dragg_mpc_env_reset alone on
+synthetic rows against their numpy restatements (`vector.env_file_reference`, `vector.env_reset_reference`), and
+`rl.DeviceVectorEnv` in closed loops against the existing `rl.VectorEnv` (two `VectorAggregator`s with the same
+seeds and starts), bit for bit.  Community: tests/test_gpu_vector.py's (16 homes of all four types, H = 24,
+April)."""
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from dragg_amd import _lib as L
+from tests.test_gpu_vector import community                       # noqa: F401  (the module's fixture)
+
+pytestmark = pytest.mark.gpu
+
+STATE = ("clock", "tracked", "max_load", "min_load", "obs", "status_hist", "path_hist", "hist", "agg_hist")
+SEEDS = (5, 6, 2 ** 40 + 7, 9)
+STARTS = (0, 7, 12, 3)
+
+
+def _bits(x):
+    return x.contiguous().view(torch.int64) if x.dtype == torch.float64 else x
+
+
+def _cfg(P=12):
+    return {"agg": {"rl": {"prev_timesteps": P}},
+            "rl": {"utility": {"action_space": [-3.0, 3.0], "action_scale": 100.0}}}
+
+
+# ------------------------------------------------------------------ the kernels alone
+def _pattern_f64(shape, tag, dev):
+    """Doubles whose bits are recognisable NaN payloads (0x7ff8 | tag | index): a copy must move them as they are."""
+    n = int(np.prod(shape))
+    return (torch.arange(n, dtype=torch.int64, device=dev) + (0x7FF8000000000000 + (tag << 32))).view(torch.float64).reshape(shape)
+
+
+def _synthetic(community, dev, E, Nb, T, P, seed=0):
+    """A grouped batch of E x Nb homes and an environment state whose every array holds a recognisable pattern."""
+    from dragg_amd.mpc import MPCBatch
+    homes, (oat, ghi, tou) = community
+    b = MPCBatch(homes[:Nb], oat, ghi, tou, 0, [0.0], groups=E)
+    N = E * Nb
+    g = torch.Generator().manual_seed(seed)
+
+    def rnd(*shape):
+        return (torch.rand(*shape, generator=g, dtype=torch.float64) * 40.0).to(dev)
+    st = types.SimpleNamespace(
+        num_timesteps=T, prev_timesteps=P, max_poss_load=61.7, start_load=3.0 * Nb,
+        clock=torch.arange(100, 100 + E, dtype=torch.int32, device=dev), tracked=rnd(E, P), max_load=rnd(E) + 20.0,
+        min_load=rnd(E) - 20.0, obs=rnd(5, E),
+        status_hist=torch.arange(T * N, dtype=torch.int32, device=dev).reshape(T, N) + 1000,
+        path_hist=torch.arange(T * N, dtype=torch.int32, device=dev).reshape(T, N) + 5000,
+        hist=_pattern_f64((T, L.NVAL, N), 1, dev), agg_hist=rnd(T, E, 3))
+    b.status.copy_(torch.arange(N, dtype=torch.int32, device=dev) + 7)
+    b.int_path.copy_(torch.arange(N, dtype=torch.int32, device=dev) + 70)
+    b.vals.copy_(_pattern_f64((L.NVAL, N), 2, dev))
+    b.fc_store.copy_(_pattern_f64((N, L.NFC, b.H), 3, dev))
+    row = _pattern_f64((L.NVAL, N), 4, dev)
+    row[0] = rnd(N)                                              # (and ordinary numbers)
+    return b, st, row, rnd
+
+
+def _host(st):
+    out = {k: getattr(st, k) for k in ("num_timesteps", "prev_timesteps", "max_poss_load", "start_load")}
+    out.update({k: getattr(st, k).cpu().numpy().copy() for k in STATE})
+    return out
+
+
+def _equal(st, ref, what):
+    for k in STATE:
+        got = getattr(st, k).cpu().numpy()
+        view = np.int64 if got.dtype == np.float64 else got.dtype
+        assert np.array_equal(got.view(view), ref[k].view(view)), (what, k)
+
+
+@pytest.mark.parametrize("Nb", [3, 4])             # (odd: 4- and 8-byte copy units; 4: 16-byte units)
+def test_env_file_and_reset_alone_equal_the_restatements(gpu, community, Nb):
+    from dragg_amd.vector import env_file_reference, env_reset_reference
+    E, T, P = 3, 5, 12
+    b, st, row, rnd = _synthetic(community, gpu, E, Nb, T, P)
+    sums = rnd(E, 3)
+    ran = torch.tensor([2, -1, 7], dtype=torch.int32, device=gpu)          # (7 >= T: as idle as -1)
+    ref = _host(st)
+    before = {k: v.copy() for k, v in ref.items() if k in STATE}
+    env_file_reference(ref, ran.cpu().numpy(), sums.cpu().numpy(), b.status.cpu().numpy(), b.int_path.cpu().numpy(),
+                       row.cpu().numpy())
+    b.env_file(st, ran, sums, hist=row)
+    torch.cuda.synchronize()
+    _equal(st, ref, "env_file")
+    # (the restatement itself left groups 1 and 2 alone, and filed group 0)
+    cols = slice(Nb, E * Nb)
+    for k in ("status_hist", "path_hist", "hist"):
+        assert np.array_equal(ref[k][..., cols].view(np.int64 if k == "hist" else np.int32),
+                              before[k][..., cols].view(np.int64 if k == "hist" else np.int32)), k
+    for k in ("clock", "max_load", "min_load"):
+        assert np.array_equal(ref[k][1:], before[k][1:]), k
+    assert np.array_equal(ref["tracked"][1:], before["tracked"][1:]) and np.array_equal(ref["obs"][:, 1:], before["obs"][:, 1:])
+    assert np.array_equal(ref["agg_hist"][:, 1:], before["agg_hist"][:, 1:])
+    assert ref["clock"][0] == 3 and ref["obs"][4, 0] == 3.0
+    assert np.array_equal(ref["status_hist"][2, :Nb], np.arange(Nb) + 7)
+    assert np.array_equal(ref["hist"][2][:, :Nb].view(np.int64), row.cpu().numpy()[:, :Nb].view(np.int64))
+    # the reset of group 1 alone
+    vals, fc = b.vals.cpu().numpy().copy(), b.fc_store.cpu().numpy().copy()
+    mask = torch.tensor([False, True, False], device=gpu)
+    env_reset_reference(ref, mask.cpu().numpy(), vals, fc)
+    b.env_reset(st, mask)
+    torch.cuda.synchronize()
+    _equal(st, ref, "env_reset")
+    assert np.array_equal(b.vals.cpu().numpy().view(np.int64), vals.view(np.int64))
+    assert np.array_equal(b.fc_store.cpu().numpy().view(np.int64), fc.view(np.int64))
+    # the NaN a reset stores is torch.full's
+    nan = torch.full((1,), float("nan"), dtype=torch.float64).view(torch.int64).item()
+    assert set(vals[:, Nb:2 * Nb].view(np.int64).reshape(-1).tolist()) == {nan}
+    assert ref["clock"].tolist() == [3, 0, 102] and ref["obs"][0, 1] == 3.0 * Nb
+    assert ref["max_load"][1] == ref["min_load"][1] == 3.0 * Nb
+
+
+@pytest.mark.parametrize("P", [1, 7, 8, 9, 12, 24, 128])
+def test_setpoint_rule_over_30_steps(gpu, community, P):
+    """The device setpoint (numpy's pairwise sum order, the shift, the max / min rule with timestep % 24 == 0)
+    against the restatement, which calls `rl.setpoint_update` itself; group 1 pauses for a few steps."""
+    from dragg_amd.vector import env_file_reference, env_reset_reference
+    E, Nb, T = 3, 3, 30
+    b, st, row, rnd = _synthetic(community, gpu, E, Nb, T, P, seed=P)
+    ref = _host(st)
+    vals, fc = b.vals.cpu().numpy().copy(), b.fc_store.cpu().numpy().copy()
+    mask = torch.ones(E, dtype=torch.bool, device=gpu)
+    env_reset_reference(ref, mask.cpu().numpy(), vals, fc)
+    b.env_reset(st, mask)
+    status, path, row_h = b.status.cpu().numpy(), b.int_path.cpu().numpy(), row.cpu().numpy()
+    clock = np.zeros(E, dtype=np.int32)
+    for k in range(T + 4):
+        on = (clock < T) & ~((np.arange(E) == 1) & (5 <= k < 9))
+        ran_h = np.where(on, clock, -1).astype(np.int32)
+        sums = rnd(E, 3)
+        env_file_reference(ref, ran_h, sums.cpu().numpy(), status, path, row_h)
+        b.env_file(st, torch.as_tensor(ran_h).to(gpu), sums, hist=row)
+        clock += on
+    torch.cuda.synchronize()
+    _equal(st, ref, P)
+    assert ref["clock"].tolist() == [T] * E
+
+
+def test_env_entry_points_refuse_bad_arguments(gpu, community):
+    E, Nb, T, P = 3, 3, 5, 12
+    b, st, row, rnd = _synthetic(community, gpu, E, Nb, T, P)
+    lib = L.load()
+    stream = L.stream_ptr(None, b.device)
+    sums = rnd(E, 3)
+    ran = torch.full((E,), -1, dtype=torch.int32, device=gpu)
+    mask = torch.zeros(E, dtype=torch.bool, device=gpu)
+    out = L.Out(status=L.ptr(b.status), hist=L.ptr(row), int_path=L.ptr(b.int_path))
+
+    def env(**kw):
+        e = b._env(st, ran, sums)
+        for k, v in kw.items():
+            setattr(e, k, v)
+        return e
+    assert lib.dragg_mpc_env_file(b.dims, env(), out, stream) == 0
+    assert lib.dragg_mpc_env_file(b.dims, None, out, stream) == -1
+    for k in ("ran", "clock", "sums", "obs"):
+        assert lib.dragg_mpc_env_file(b.dims, env(**{k: None}), out, stream) == -1, k
+    for k in ("clock", "obs"):
+        assert lib.dragg_mpc_env_reset(b.dims, env(**{k: None}), L.ptr(mask), b._hash(), stream) == -1, k
+    assert lib.dragg_mpc_env_reset(b.dims, env(), None, b._hash(), stream) == -1
+    for bad in (dict(prev_timesteps=0), dict(prev_timesteps=129), dict(num_timesteps=0), dict(hist=None),
+                dict(ran=L.ptr(st.clock))):
+        assert lib.dragg_mpc_env_file(b.dims, env(**bad), out, stream) == -1, bad
+    assert lib.dragg_mpc_env_file(b.dims, env(), L.Out(status=L.ptr(b.status), int_path=L.ptr(b.int_path)), stream) == -1
+    d = L.Dims.from_buffer_copy(b.dims)
+    d.n_groups = 2                                               # 9 homes
+    assert lib.dragg_mpc_env_file(d, env(), out, stream) == -1
+    assert lib.dragg_mpc_env_reset(d, env(), L.ptr(mask), b._hash(), stream) == -1
+    d.n_homes, d.n_groups = 0, 0
+    assert lib.dragg_mpc_env_file(d, env(), out, stream) == 0
+    assert lib.dragg_mpc_env_reset(d, env(), L.ptr(mask), b._hash(), stream) == 0
+    ref = _host(st)
+    torch.cuda.synchronize()
+    _equal(st, ref, "nothing ran")
+
+
+# ------------------------------------------------------------------ closed loops against the existing environment
+def _pair(community, T, P=12):
+    from dragg_amd.rl import DeviceVectorEnv, VectorEnv
+    from dragg_amd.vector import VectorAggregator
+    homes, (oat, ghi, tou) = community
+    vas = [VectorAggregator(homes, oat, ghi, tou, 4, list(SEEDS), list(STARTS), T) for _ in range(2)]
+    return VectorEnv(vas[0], _cfg(P)), DeviceVectorEnv(vas[1], _cfg(P))
+
+
+def _same_obs(obs_h, obs_d, what):
+    for k in L.OBS_KEYS:
+        h = torch.as_tensor(np.asarray(obs_h[k], dtype=np.float64))
+        assert obs_d[k].is_cuda and torch.equal(_bits(h), _bits(obs_d[k].cpu())), (what, k)
+
+
+def _same_state(host, dev, what):
+    a, b = host.va, dev.va
+    assert a.clocks.cpu().tolist() == b.clocks.cpu().tolist(), what
+    for x, y, k in ((a.batch.vals, b.batch.vals, "vals"), (a.batch.fc_store, b.batch.fc_store, "fc"),
+                    (a.hist, b.hist, "hist"), (a.status_hist, b.status_hist, "status_hist"),
+                    (a.path_hist, b.path_hist, "path_hist"), (a.agg_hist, b.agg_hist, "agg_hist")):
+        assert torch.equal(_bits(x), _bits(y)), (what, k)
+
+
+def test_closed_loop_equals_the_existing_environment(gpu, community):
+    """E = 4, T = 27, P = 12: `VectorEnv` with `act_vector` against `DeviceVectorEnv` with `act_device`; episode 1
+    starts over at step 3 with a new seed (a device mask on the new path), episode 2 is parked during steps
+    5-7; the others sit idle until the two are done.  Every episode crosses timestep 24.  At least half of the
+    home-steps must be optimal (measured: 972 of 1,728), so the run is not all fallbacks."""
+    from dragg_amd.rl import SetpointAgent
+    T = 27
+    host, dev = _pair(community, T)
+    ag_h, ag_d = SetpointAgent(_cfg()), SetpointAgent(_cfg())
+    obs_h, obs_d = host.reset(), dev.reset()
+    _same_obs(obs_h, obs_d, "reset")
+    one = torch.tensor([False, True, False, False], device=gpu)
+    two = torch.tensor([False, False, True, False], device=gpu)
+    k = 0
+    while not host.done().all():
+        if k == 3:
+            obs_h = host.reset([1], seeds=[0, 77, 0, 0])
+            obs_d = dev.reset(one, seeds=torch.tensor([0, 77, 0, 0], device=gpu))
+            ag_h.reset_vector([False, True, False, False])
+            ag_d.reset_device(one)
+            _same_obs(obs_h, obs_d, "masked reset")
+        if k == 5:
+            host.park([2])
+            dev.park(two)
+        if k == 8:
+            host.resume([2])
+            dev.resume(two)
+        p_h, p_d = ag_h.act_vector(obs_h), ag_d.act_device(obs_d)
+        assert p_d.is_cuda and torch.equal(_bits(torch.as_tensor(p_h)), _bits(p_d.cpu())), k
+        obs_h, done_h = host.step(p_h)
+        obs_d, done_d = dev.step(p_d)
+        assert done_d.is_cuda and done_d.dtype == torch.bool and done_h.tolist() == done_d.cpu().tolist(), k
+        _same_obs(obs_h, obs_d, k)
+        assert host.va.clocks.cpu().tolist() == dev.va.clocks.cpu().tolist(), k
+        k += 1
+        assert k <= T + 3
+    assert k == T + 3 and obs_h["timestep"].tolist() == [T] * 4
+    _same_state(host, dev, "end")
+    st = dev.va.status_hist
+    n_opt = int((st == L.ST_OPTIMAL).sum())
+    print("optimal home-steps of the closed loop:", n_opt, "of", st.numel())
+    assert n_opt * 2 >= st.numel()
+
+
+def test_step_swept_equals_the_existing_environment(gpu, community):
+    from dragg_amd.rl import SweepAgent
+    host, dev = _pair(community, 4)
+    agent = SweepAgent(_cfg(), n_candidates=3)
+    obs_h, obs_d = host.reset(), dev.reset()
+    for k in range(4):
+        if k == 2:
+            host.park([3])
+            dev.park([3])
+        obs_h, done_h = host.step_swept(agent.act_vector(obs_h))
+        obs_d, done_d = dev.step_swept(agent.act_device(obs_d))
+        assert dev.choice.is_cuda and dev.choice.dtype == torch.int32
+        assert host.choice.tolist() == dev.choice.cpu().tolist(), k
+        assert done_h.tolist() == done_d.cpu().tolist()
+        _same_obs(obs_h, obs_d, k)
+        _same_state(host, dev, k)
+    assert host.choice.tolist()[3] == -1 and host.va.clocks_host() == [4, 4, 4, 2]
+
+
+def test_no_host_round_trip(gpu, community):
+    """`reset(done())`, `step` and `step_swept` of the new environment, with the policies' device calls, while
+    torch's synchronisation debug mode raises on every host synchronisation (the tensors the calls take are
+    built before: an upload from host memory synchronises)."""
+    from dragg_amd.rl import DeviceVectorEnv, SetpointAgent, SweepAgent
+    from dragg_amd.vector import VectorAggregator
+    homes, (oat, ghi, tou) = community
+    va = VectorAggregator(homes, oat, ghi, tou, 4, list(SEEDS), list(STARTS), 2)
+    env = DeviceVectorEnv(va, _cfg())
+    pi, sw = SetpointAgent(_cfg()), SweepAgent(_cfg(), n_candidates=3)
+    obs = env.reset()
+    cands = sw.act_device(obs)
+    seeds = torch.tensor([21, 22, 23, 24], device=gpu)
+    starts = torch.tensor([1, 2, 3, 4], dtype=torch.int32, device=gpu)
+    obs, _ = env.step(pi.act_device(obs))                    # (the first calls: code objects, workspaces)
+    obs, _ = env.step_swept(cands)
+    torch.cuda.synchronize()
+    mode = torch.cuda.get_sync_debug_mode()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        obs = env.reset(env.done(), seeds=seeds, start_indices=starts)
+        pi.reset_device(env.done())
+        obs, done = env.step(pi.act_device(obs))
+        obs, done = env.step_swept(sw.act_device(obs))
+        env.park(done)
+        env.resume(done)
+    finally:
+        torch.cuda.set_sync_debug_mode(mode)
+    assert va.clocks_host() == [2] * 4 and bool(done.all())
+    assert va.seeds.cpu().tolist() == [21, 22, 23, 24] and int(env.choice.min()) >= 0
