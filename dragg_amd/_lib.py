@@ -100,6 +100,52 @@ ENV_PREV_MAX = 128             # DRAGG_ENV_PREV_MAX: the tracked loads the devic
 OBS_KEYS = ("agg_load", "forecast_load", "agg_cost", "agg_setpoint", "timestep")    # rows of dragg_mpc_env.obs
 
 
+class Plan(ctypes.Structure):
+    """dragg_mpc_plan: the masks of the chosen forecast keys and vals rows, and the outputs of
+    dragg_mpc_plan_groups (curve / count [G][nk][H], stats [G][nr][4])."""
+    _fields_ = [("fc_keys", ctypes.c_uint32), ("val_rows", ctypes.c_uint32), ("curve", c_dp), ("count", c_dp),
+                ("stats", c_dp)]
+
+
+PLAN_WAYS = 16                 # DRAGG_PLAN_WAYS: the partial sums of a plan entry (part of its summation order)
+# the forecast keys a plan curve can hold (dragg_fc_key, bit k of dragg_mpc_plan.fc_keys) and the vals rows a plan
+# statistic can hold (dragg_val, bit r of val_rows), by their short names
+PLAN_KEYS = ("p_grid", "forecast_p_grid", "p_load", "temp_in_ev", "temp_wh_ev", "hvac_cool", "hvac_heat", "wh_heat",
+             "cost", "waterdraws", "p_pv", "u_pv_curt", "p_batt_ch", "p_batt_disch", "e_batt")
+PLAN_ROWS = PLAN_KEYS + ("temp_in_opt", "temp_wh_opt", "correct_solve", "solve_counter")
+PLAN_STATS = ("count", "sum", "min", "max")                     # the last axis of dragg_mpc_plan.stats
+
+
+def plan_select(keys, rows=()):
+    """The chosen forecast keys and vals rows -- each a short name (PLAN_KEYS / PLAN_ROWS), a hash field name
+    (FC_KEYS / VAL_KEYS) or an index -- as (fc_keys mask, val_rows mask, key indices, row indices).  The indices
+    are ascending and without repeats whatever the order given: that is the order of the outputs' key axis."""
+    def pick(items, short, long, what):
+        if isinstance(items, (str, int)):
+            items = (items,)
+        idx = set()
+        for x in items:
+            if isinstance(x, str):
+                if x not in short and x not in long:
+                    raise ValueError(f"{x!r} is no {what} (one of {list(short)})")
+                x = short.index(x) if x in short else long.index(x)
+            if not 0 <= int(x) < len(short):
+                raise ValueError(f"{what} index {x} outside 0..{len(short) - 1}")
+            idx.add(int(x))
+        idx = sorted(idx)
+        return sum(1 << i for i in idx), idx
+    km, ki = pick(keys, PLAN_KEYS, FC_KEYS, "plan key")
+    rm, ri = pick(rows, PLAN_ROWS, VAL_KEYS, "plan row")
+    return km, rm, ki, ri
+
+
+def plan_shape(keys, rows=(), G=1, H=1):
+    """The shapes of dragg_mpc_plan_groups' outputs for these keys and rows: (curve and count [G][nk][H], stats
+    [G][nr][4])."""
+    _, _, ki, ri = plan_select(keys, rows)
+    return (int(G), len(ki), int(H)), (int(G), len(ri), len(PLAN_STATS))
+
+
 class Lag(ctypes.Structure):
     _fields_ = [("clock", c_dp), ("skipped", c_dp), ("narrow", c_dp), ("side_workspace", c_dp)]
 
@@ -149,7 +195,7 @@ EXPORTS = ["dragg_mpc_abi_version", "dragg_mpc_strerror", "dragg_mpc_lds_bytes",
            "dragg_mpc_side_workspace_bytes", "dragg_mpc_side_grid", "dragg_mpc_source_hash",
            "dragg_mpc_replicate", "dragg_mpc_aggregate_groups", "dragg_mpc_step_episodes",
            "dragg_mpc_season_noise_episodes", "dragg_mpc_adopt", "dragg_mpc_select_groups", "dragg_mpc_env_file",
-           "dragg_mpc_env_reset"]
+           "dragg_mpc_env_reset", "dragg_mpc_plan_groups"]
 
 _LIB = None
 
@@ -221,6 +267,7 @@ def load(path=LIB_PATH):
                                             c_dp, c_dp]
     lib.dragg_mpc_env_file.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Env), ctypes.POINTER(Out), c_dp]
     lib.dragg_mpc_env_reset.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Env), c_dp, ctypes.POINTER(Hash), c_dp]
+    lib.dragg_mpc_plan_groups.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Hash), ctypes.POINTER(Plan), c_dp]
     if lib.dragg_mpc_abi_version() != ABI_VERSION:
         raise DraggError("ABI version mismatch between dragg_amd and libdragg_mi355x.so")
     if not os.environ.get("DRAGG_LIB"):

@@ -402,6 +402,44 @@ class DeviceAggregator:
         self._gen += 1
         self._hold = None
 
+    # ------------------------------------------------------------------ plan observations
+    # The open-loop plan the last solves left in the hash arrays, reduced on the device
+    # (dragg_mpc_plan_groups): what the homes will do over the horizon unless the price changes.  Not
+    # `forecast`'s closed-loop rollout: nothing is solved.
+    def _reduce_plan(self, out):
+        """This shard's (curve, count, stats) all-reduced over the ranks: sums and counts SUM, min MIN, max MAX."""
+        if self.world > 1:
+            curve, count, stats = out
+            op = torch.distributed.ReduceOp
+            torch.distributed.all_reduce(curve, group=self.group)
+            torch.distributed.all_reduce(count, group=self.group)
+            head, mn, mx = stats[..., :2].contiguous(), stats[..., 2].contiguous(), stats[..., 3].contiguous()
+            torch.distributed.all_reduce(head, group=self.group)
+            torch.distributed.all_reduce(mn, op=op.MIN, group=self.group)
+            torch.distributed.all_reduce(mx, op=op.MAX, group=self.group)
+            stats[..., :2], stats[..., 2], stats[..., 3] = head, mn, mx
+        return out
+
+    def plan(self, keys, rows=()):
+        """The live community's planned curves as one group -> device tensors (curve [1][nk][H], count
+        [1][nk][H], stats [1][nr][4]: count, sum, min, max): `MPCBatch.plan_groups` of this shard after
+        `drain()`, all-reduced over the ranks.  On one rank the sums are in the kernel's fixed order (16 ways,
+        then a tree) over the whole community; with more ranks each shard is summed in that order and the
+        shards are then added by the all-reduce, so a multi-rank sum is no longer the 16-way order of the whole
+        community: it equals it to rounding only.  Counts, min and max are exact either way."""
+        self.drain()
+        return self._reduce_plan(self.batch.plan_groups(keys, rows))
+
+    def sweep_plan(self, keys, rows=()):
+        """The planned curves of the held sweep's G replicas -> (curve [G][nk][H], count, stats [G][nr][4]):
+        candidate g's open-loop response over the whole horizon, where `sweep` returns its first-step sums.
+        The held step is the sweep's first (with steps == 1 the replica batch itself, with more the arrays
+        cloned after it: `HeldStep`), so replica g's rows are those `plan()` gives after `commit(g)`, bit for
+        bit.  All-reduced over the ranks as `plan`.  ValueError where `holds()` is false."""
+        if not self.holds():
+            raise ValueError("sweep_plan: no sweep of the live state is held (sweep(..., hold=True) first)")
+        return self._reduce_plan(self.batch.plan_groups(keys, rows, src=self._hold["src"]))
+
     # ------------------------------------------------------------------ checkpoint / resume
     # The reference has no resume (aggregator.py:265-267, 768: a stopped run starts over); here a
     # checkpoint is the device state a step reads -- the hash arrays, the timestep, the reward

@@ -5265,6 +5265,121 @@ __global__ __launch_bounds__(REP_NT) void env_reset_kernel(EnvArgs a) {
     if (blockIdx.x == 0 && threadIdx.x == 0) env_setpoint(a, g, 0, a.start_load, a.start_load, 0.0, true);
 }
 
+// Plan observations (dragg_mpc_plan_groups): per group the time-aligned horizon curves of the chosen forecast
+// keys and the statistics of the chosen vals rows, in the header's summation order.  An ENTRY is one output
+// sum: (key k, stage j) of a curve, or a vals row (which reads like a stage-0 entry: vals[row][n]).  Block
+// (x, g) owns 64 entries of group g -- the curve's nk * H entries flattened key-major, 64 per block, then one
+// block for the up to 19 rows -- and has one wave per way: wave w walks homes w, w + 16, ... in ascending order,
+// lane = entry, so the lanes of a wave read one home's H doubles of a key as one contiguous run (8-byte loads:
+// the shift c leaves the run 8-byte aligned only) and every lane keeps its own partial in a register.  The
+// home's counter is one broadcast load per wave.  PLAN_UNROLL homes' loads are issued before their adds (the
+// adds stay in order): the kernel is bound by the latency of these rounds, not by bytes.  The 16 partials of an entry meet in LDS; wave 0 adds them as the balanced tree and
+// stores the entry.  No block reads what another writes: no atomics, no handshake.
+constexpr int PLAN_NT = DRAGG_PLAN_WAYS * WAVE;
+constexpr int PLAN_UNROLL = 16;         // (32 spills at 1,024 threads; at 10k homes a way is 625 homes: 40 rounds)
+static_assert(DRAGG_PLAN_WAYS == 16, "the tree below pairs 16 partials");
+struct PlanArgs {
+    const double* vals;
+    const double* fc;
+    double* curve;
+    int32_t* count;
+    double* stats;
+    int N, Nb, H;
+    int nk, nr;
+    int curve_blocks;                   // blocks of a group that own curve entries; the next one owns the rows
+    unsigned char key[DRAGG_NFC];       // the chosen keys, ascending
+    unsigned char row[DRAGG_NVAL];      // the chosen rows, ascending
+};
+__global__ __launch_bounds__(PLAN_NT) void plan_groups_kernel(PlanArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double p_sum[DRAGG_PLAN_WAYS][WAVE], p_min[DRAGG_PLAN_WAYS][WAVE], p_max[DRAGG_PLAN_WAYS][WAVE];
+    __shared__ int p_cnt[DRAGG_PLAN_WAYS][WAVE];
+    const int w = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+    const int g = (int)blockIdx.y;
+    const int H = a.H, Nb = a.Nb;
+    const bool rows = (int)blockIdx.x >= a.curve_blocks;
+    const int e = rows ? lane : (int)blockIdx.x * WAVE + lane;
+    const bool live = e < (rows ? a.nr : a.nk * H);
+    const int k = !live ? 0 : rows ? a.row[e] : a.key[e / H];
+    const int j = !live || rows ? 0 : e % H;
+    const size_t col = (size_t)g * Nb;
+    const double* v0 = a.vals + (size_t)k * a.N + col;                          // stage 0 / a row: vals[k][n]
+    const double* cn = a.vals + (size_t)DRAGG_V_SOLVE_COUNTER * a.N + col;
+    const size_t home = (size_t)DRAGG_NFC * H;
+    const double* f = j > 0 ? a.fc + (col * DRAGG_NFC + k) * H + j : nullptr;   // + i * home + c: fc[n][k][c + j]
+    const double nan = __builtin_nan("");
+    double s = 0.0, mn = __builtin_inf(), mx = -__builtin_inf();
+    int n = 0;
+    if (live) {
+        for (int i0 = w; i0 < Nb; i0 += DRAGG_PLAN_WAYS * PLAN_UNROLL) {
+            double v[PLAN_UNROLL];
+            if (j == 0) {
+#pragma unroll
+                for (int u = 0; u < PLAN_UNROLL; ++u) {
+                    const int i = i0 + u * DRAGG_PLAN_WAYS;
+                    v[u] = i < Nb ? v0[i] : nan;
+                }
+            } else {
+                // two rounds of independent loads: the homes' counters, then their values (a home past the
+                // group's end counts as never solved: c = H, nothing read)
+                double cnt[PLAN_UNROLL];
+#pragma unroll
+                for (int u = 0; u < PLAN_UNROLL; ++u) {
+                    const int i = i0 + u * DRAGG_PLAN_WAYS;
+                    cnt[u] = i < Nb ? cn[i] : nan;
+                }
+#pragma unroll
+                for (int u = 0; u < PLAN_UNROLL; ++u) {
+                    const int i = i0 + u * DRAGG_PLAN_WAYS;
+                    const int c = cnt[u] >= 0.0 && cnt[u] < (double)H ? (int)cnt[u] : H;    // (NaN: H)
+                    v[u] = c + j < H ? f[(size_t)i * home + c] : nan;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < PLAN_UNROLL; ++u) {
+                const double x = v[u];
+                if (x == x) {                      // NaN: absent
+                    s += x;
+                    ++n;
+                    mn = x < mn ? x : mn;
+                    mx = x > mx ? x : mx;
+                }
+            }
+        }
+    }
+    p_sum[w][lane] = s;
+    p_cnt[w][lane] = n;
+    p_min[w][lane] = mn;
+    p_max[w][lane] = mx;
+    __syncthreads();
+    if (w != 0 || !live) return;
+    double t[DRAGG_PLAN_WAYS];
+#pragma unroll
+    for (int m = 0; m < DRAGG_PLAN_WAYS; ++m) t[m] = p_sum[m][lane];
+#pragma unroll
+    for (int width = DRAGG_PLAN_WAYS / 2; width >= 1; width /= 2)          // p[2m] + p[2m + 1], level by level
+#pragma unroll
+        for (int m = 0; m < width; ++m) t[m] = t[2 * m] + t[2 * m + 1];
+    n = 0;
+#pragma unroll
+    for (int m = 0; m < DRAGG_PLAN_WAYS; ++m) {
+        n += p_cnt[m][lane];
+        mn = p_min[m][lane] < mn ? p_min[m][lane] : mn;
+        mx = p_max[m][lane] > mx ? p_max[m][lane] : mx;
+    }
+    if (rows) {
+        double* o = a.stats + ((size_t)g * a.nr + e) * 4;
+        o[0] = (double)n;
+        o[1] = t[0];
+        o[2] = mn;
+        o[3] = mx;
+    } else {
+        const size_t o = (size_t)g * a.nk * H + e;
+        a.curve[o] = t[0];
+        a.count[o] = n;
+    }
+}
+
 // (nb: the base homes of a grouped batch, N otherwise.  Home r of group g = r / nb draws the stream of
 // (ep.seed[g] -- NULL: seed --, its base home, ep.timestep[g] -- NULL: t); the columns of a group whose own
 // timestep is negative are left as they are)
@@ -5977,6 +6092,37 @@ int dragg_mpc_env_reset(const dragg_mpc_dims* dims, const dragg_mpc_env* env, co
     if (env->agg_hist) ok = ok && env_seg(a, nullptr, env->agg_hist, 3 * 8, T, 8, 0);
     if (!ok) return DRAGG_E_ARG;
     return env_launch(env_reset_kernel, a, stream);
+}
+
+int dragg_mpc_plan_groups(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, const dragg_mpc_plan* plan,
+                          void* stream) {
+    if (!dims || !hash || !plan || dims->n_homes < 0 || dims->horizon < 1) return DRAGG_E_ARG;
+    if ((plan->fc_keys >> DRAGG_NFC) != 0 || (plan->val_rows >> DRAGG_NVAL) != 0) return DRAGG_E_ARG;
+    const int G = group_count(dims);
+    if (G < 0 || G > 65535) return DRAGG_E_ARG;        // (a grid row per group)
+    if (plan->fc_keys && (!plan->curve || !plan->count)) return DRAGG_E_ARG;
+    if (plan->val_rows && !plan->stats) return DRAGG_E_ARG;
+    if (dims->n_homes > 0 && (!hash->vals || (plan->fc_keys && !hash->fc))) return DRAGG_E_ARG;
+    if (!plan->fc_keys && !plan->val_rows) return DRAGG_OK;
+    PlanArgs a{};
+    a.vals = hash->vals;
+    a.fc = hash->fc;
+    a.curve = plan->curve;
+    a.count = plan->count;
+    a.stats = plan->stats;
+    a.N = dims->n_homes;
+    a.Nb = dims->n_homes / G;
+    a.H = dims->horizon;
+    for (int k = 0; k < DRAGG_NFC; ++k)
+        if (plan->fc_keys >> k & 1u) a.key[a.nk++] = (unsigned char)k;
+    for (int r = 0; r < DRAGG_NVAL; ++r)
+        if (plan->val_rows >> r & 1u) a.row[a.nr++] = (unsigned char)r;
+    const long long entries = (long long)a.nk * a.H;
+    const long long blocks = (entries + WAVE - 1) / WAVE + (a.nr ? 1 : 0);
+    if (blocks > 0x7FFFFFFFLL) return DRAGG_E_ARG;
+    a.curve_blocks = (int)((entries + WAVE - 1) / WAVE);
+    hipLaunchKernelGGL(plan_groups_kernel, dim3((unsigned)blocks, (unsigned)G), dim3(PLAN_NT), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
 }
 
 }  // extern "C"

@@ -487,6 +487,43 @@ class MPCBatch:
             self._call(self.lib.dragg_mpc_aggregate_groups, self._hash(), L.ptr(self.agg_groups), stream=stream)
             return self.agg_groups
 
+    # ------------------------------------------------------------------ plan observations
+    def plan_groups(self, keys, rows=(), out=None, stream=None, src=None):
+        """The planned curves of every group (dragg_mpc_plan_groups) -> (curve [G][nk][H] float64, count
+        [G][nk][H] int32, stats [G][nr][4] float64: count, sum, min, max) as device tensors.  `keys`: the forecast
+        keys whose time-aligned horizon curve is summed over each group's homes, `rows`: the vals rows whose
+        statistics are taken (names of L.PLAN_KEYS / L.PLAN_ROWS or indices; the outputs hold them in ascending
+        index order).  Entry 0 of a curve is the collected value, entry j the homes' plan j stages ahead of the
+        wall clock (a home in fallback: its stale plan, shifted by its solve counter); absent values (NaN) add
+        nothing and `count` says how many homes stand behind each sum.  The summation order is fixed (16 partial
+        sums over homes w, w + 16, ..., then a balanced tree: `vector.plan_groups_reference`), so a group's rows
+        do not depend on the batch around it.  The hash arrays are only read.  `out`: a (curve, count, stats)
+        triple to write into instead of new tensors; `src`: another holder of hash arrays of this horizon (vals,
+        fc_store, N, groups -- a held sweep's replicas) in place of this batch's.  No synchronisation."""
+        km, rm, ki, ri = L.plan_select(keys, rows)
+        b = self if src is None else src
+        G = max(int(getattr(b, "groups", 1)), 1)
+        if b.H != self.H:
+            raise ValueError(f"plan_groups: a source of horizon {b.H}, not {self.H}")
+        shapes = {"curve": ((G, len(ki), self.H), torch.float64), "count": ((G, len(ki), self.H), torch.int32),
+                  "stats": ((G, len(ri), len(L.PLAN_STATS)), torch.float64)}
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = tuple(torch.empty(s, dtype=d, device=self.device) for s, d in shapes.values())
+            for t, (name, (s, d)) in zip(out, shapes.items()):
+                if not torch.is_tensor(t) or t.device != self.device or t.dtype != d or tuple(t.shape) != s \
+                        or not t.is_contiguous():
+                    raise ValueError(f"plan_groups: out's {name} must be a contiguous device tensor {list(s)} of {d}")
+            if src is None:
+                self.drain(stream)
+            dims = L.Dims.from_buffer_copy(self.dims)
+            dims.n_homes, dims.n_groups = int(b.N), G if G > 1 else 0
+            plan = L.Plan(fc_keys=km, val_rows=rm, curve=L.ptr(out[0]), count=L.ptr(out[1]), stats=L.ptr(out[2]))
+            L.check(self.lib.dragg_mpc_plan_groups(dims, L.Hash(vals=L.ptr(b.vals), fc=L.ptr(b.fc_store)), plan,
+                                                   L.stream_ptr(stream, self.device)))
+            self._keep = (src, out)
+            return tuple(out)
+
     # ------------------------------------------------------------------ device-resident environment
     def _env(self, st, ran=None, sums=None):
         """The dragg_mpc_env struct of an environment state (`dragg_amd.vector.EnvState`: scalars, the state

@@ -10,6 +10,8 @@ with its own seed, start index, clock and price, for policies that learn over ma
 (`SetpointAgent.train_vector`).  `DeviceVectorEnv` (`Aggregator.rl_vector(E, device_env=True)`) is the same
 environment with its state, observations, done flags and choices kept on the device, for policies that are
 device code themselves (`SetpointAgent.act_device`, `SweepAgent.act_device`): no step or reset synchronises.
+With `plan_keys` its observations also hold the community's planned curves over the horizon per episode (the
+open-loop plan the last solves left on the device, one more launch per step).
 
 The reference's learning agent (`dragg/agent.py`, an abstract actor-critic whose
 `calc_state` / `reward` are left to a subclass and which no driver of v1 calls) is out of
@@ -279,9 +281,19 @@ class DeviceVectorEnv:
     device masks (`env.reset(env.done())`), and `reset` takes `seeds` / `start_indices` as device tensors [E],
     used for the masked episodes without a host check: a start index outside the environment window leaves that
     episode idle.  Host lists are taken and checked as in `VectorEnv`.  `agg.rl.prev_timesteps` must lie in
-    1..128."""
+    1..128.
 
-    def __init__(self, vector_aggregator, config, max_poss_load=None, n_homes=None):
+    Plan observations (`plan_keys`, `plan_rows`: names of `_lib.PLAN_KEYS` / `_lib.PLAN_ROWS`; default none): every
+    `reset`, `step` and `step_swept` then ends with one more launch (dragg_mpc_plan_groups) into buffers allocated
+    once, and `observations()` gains `plan` [E][nk][H] -- per episode the community's planned curve of each key
+    over the horizon, entry 0 the step's collected value, keys in ascending index order (`plan_key_names`) --,
+    `plan_count` [E][nk][H] (int32: the homes behind each entry) and `plan_stats` [E][nr][4] (count, sum, min, max
+    of each vals row), views like the others.  It is the open-loop plan of the episodes' last solves: a parked or
+    finished episode keeps its last step's, a fresh one's is empty (count 0).  Without them the environment issues
+    exactly the launches it issued before."""
+
+    def __init__(self, vector_aggregator, config, max_poss_load=None, n_homes=None, plan_keys=(), plan_rows=()):
+        from . import _lib as L
         from . import inputs as I
         self.va = va = vector_aggregator
         self.config = config
@@ -291,13 +303,30 @@ class DeviceVectorEnv:
         self.n_homes = va.Nb if n_homes is None else int(n_homes)
         self.state = va.env_state(self.prev_timesteps, self.max_poss_load, 3 * self.n_homes)
         self.choice = None
+        _, _, ki, ri = L.plan_select(plan_keys, plan_rows)
+        self.plan_key_names, self.plan_row_names = [L.PLAN_KEYS[k] for k in ki], [L.PLAN_ROWS[r] for r in ri]
+        self._plan = None
+        if ki or ri:
+            import torch
+            curve, stats = L.plan_shape(ki, ri, self.E, va.H)
+            self._plan = (torch.zeros(curve, dtype=torch.float64, device=va.device),
+                          torch.zeros(curve, dtype=torch.int32, device=va.device),
+                          torch.zeros(stats, dtype=torch.float64, device=va.device))
+
+    def _observe_plan(self):
+        if self._plan is not None:
+            self.va.plan(self.plan_key_names, self.plan_row_names, out=self._plan)
 
     def observations(self):
         from ._lib import OBS_KEYS
-        return {k: self.state.obs[i] for i, k in enumerate(OBS_KEYS)}
+        obs = {k: self.state.obs[i] for i, k in enumerate(OBS_KEYS)}
+        if self._plan is not None:
+            obs["plan"], obs["plan_count"], obs["plan_stats"] = self._plan
+        return obs
 
     def reset(self, mask=None, seeds=None, start_indices=None):
         self.va.reset_env(self.state, mask, seeds=seeds, start_indices=start_indices)
+        self._observe_plan()
         return self.observations()
 
     def park(self, mask):
@@ -312,6 +341,7 @@ class DeviceVectorEnv:
     def step(self, actions):
         """-> (observations, done [E]), as `VectorEnv.step`."""
         self.va.step_env(self.state, actions)
+        self._observe_plan()
         return self.observations(), self.done()
 
     def step_swept(self, candidates):
@@ -322,6 +352,7 @@ class DeviceVectorEnv:
         choice = va.select(sums, self.state.obs[3], candidates)
         va.commit_env(self.state, choice)
         self.choice = torch.where(va.adopted, choice, torch.full_like(choice, -1))
+        self._observe_plan()
         return self.observations(), self.done()
 
 

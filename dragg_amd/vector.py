@@ -19,6 +19,9 @@ environment's setpoint state and observations (dragg_mpc_env_file), and one kern
 episodes over by writing their columns alone (dragg_mpc_env_reset).  `env_file_reference` and
 `env_reset_reference` restate the two kernels on numpy arrays for the tests.
 
+`plan` reduces the plans the episodes' last solves left in the hash arrays to per-episode horizon curves
+(dragg_mpc_plan_groups; `plan_groups_reference` restates it, summation order included).
+
 One rank only: sharding episodes over ranks is not built.
 """
 import numpy as np
@@ -124,6 +127,56 @@ def env_reset_reference(env, mask, vals, fc):
         env["tracked"][g] = tracked
         env["max_load"][g], env["min_load"][g] = mx, mn
         env["obs"][:, g] = (load, load, 0.0, avg, 0)
+
+
+def plan_groups_reference(vals, fc, G, keys, rows=()):
+    """dragg_mpc_plan_groups restated on numpy arrays with explicit loops in the contract's order (the spec its
+    CPU and GPU tests share, and what a stand-in batch serves `plan_groups` with -- not a solver fallback).
+    `vals` [NVAL][N], `fc` [N][NFC][H], G groups of Nb = N / G homes -> (curve [G][nk][H] float64, count
+    [G][nk][H] int32, stats [G][nr][4] float64).  Per entry: 16 partial sums from +0.0, partial w adding the
+    present (non-NaN) values of homes w, w + 16, ... in ascending order, then the balanced tree
+    ((p0 + p1) + (p2 + p3)) + ... over the 16; min and max over the present values."""
+    _, _, ki, ri = L.plan_select(keys, rows)
+    vals, fc = np.asarray(vals, dtype=np.float64), np.asarray(fc, dtype=np.float64)
+    N, H = vals.shape[1], fc.shape[2]
+    G = max(int(G), 1)
+    if N % G:
+        raise ValueError(f"{N} homes are not {G} groups")
+    Nb, W = N // G, L.PLAN_WAYS
+    curve, count = np.zeros((G, len(ki), H)), np.zeros((G, len(ki), H), dtype=np.int32)
+    stats = np.zeros((G, len(ri), len(L.PLAN_STATS)))
+
+    def reduce(values):
+        """values: the Nb homes' doubles of one entry, NaN = absent -> (count, sum, min, max)."""
+        p = [np.float64(0.0)] * W
+        n, mn, mx = 0, np.float64(np.inf), np.float64(-np.inf)
+        for w in range(W):
+            for i in range(w, len(values), W):
+                x = np.float64(values[i])
+                if x == x:
+                    p[w] = p[w] + x
+                    n += 1
+                    mn, mx = (x if x < mn else mn), (x if x > mx else mx)
+        while len(p) > 1:
+            p = [p[2 * m] + p[2 * m + 1] for m in range(len(p) // 2)]
+        return n, p[0], mn, mx
+
+    for g in range(G):
+        cols = range(g * Nb, (g + 1) * Nb)
+        shift = []
+        for n in cols:
+            cnt = vals[L.K["solve_counter"], n]
+            shift.append(int(cnt) if 0 <= cnt < H else H)         # (NaN: H)
+        for a, k in enumerate(ki):
+            for j in range(H):
+                if j == 0:
+                    v = [vals[k, n] for n in cols]
+                else:
+                    v = [fc[n, k, c + j] if c + j < H else np.nan for n, c in zip(cols, shift)]
+                count[g, a, j], curve[g, a, j] = reduce(v)[:2]
+        for a, r in enumerate(ri):
+            stats[g, a] = reduce([vals[r, n] for n in cols])
+    return curve, count, stats
 
 
 class VectorAggregator:
@@ -430,6 +483,14 @@ class VectorAggregator:
         self._set_keys(None if mask is None else m, host.get("seeds"), host.get("start_indices"))
         self.parked = self.parked & ~m
         self.batch.env_reset(st, m.contiguous())
+
+    # ------------------------------------------------------------------ plan observations
+    def plan(self, keys, rows=(), out=None):
+        """Every episode's planned curves, from the state its last step left (`MPCBatch.plan_groups`): device
+        tensors (curve [E][nk][H], count [E][nk][H], stats [E][nr][4]).  A pure function of the hash arrays: a
+        parked or finished episode's rows are those of its last step, a fresh one's empty (count 0).  No
+        synchronisation."""
+        return self.batch.plan_groups(keys, rows, out=out)
 
     # ------------------------------------------------------------------ rows for the host
     def clocks_host(self):

@@ -461,6 +461,40 @@ int dragg_mpc_env_file(const dragg_mpc_dims* dims, const dragg_mpc_env* env, con
 int dragg_mpc_env_reset(const dragg_mpc_dims* dims, const dragg_mpc_env* env, const uint8_t* mask,
                         dragg_mpc_hash* hash, void* stream);
 
+/* Plan observations (since v10, additive): the community's planned curves per group, reduced from the hash
+   arrays every successful solve leaves on the device.  A pure function of them: reads hash.vals and hash.fc
+   only, writes plan.curve, plan.count and plan.stats only.  G = max(dims.n_groups, 1), Nb = n_homes / G;
+   home i of group g is column n = g * Nb + i.
+   The curve of forecast key k is time-aligned: with cnt = vals[DRAGG_V_SOLVE_COUNTER][n] and c = (int)cnt if
+   0 <= cnt < H, else H (NaN -- a home that never solved -- and a counter at or past H), home n contributes
+     entry 0       vals[k][n]: the collected value (collect_data's; after a success fc[n][k][0] bit for bit,
+                   after a fallback the thermostat's),
+     entry j >= 1  fc[n][k][c + j] if c + j < H, else nothing: a home in fallback contributes its stale plan at
+                   the right wall-clock stage (the index write_fallback itself reads).
+   A NaN value (a PV key of a home without PV, a field never written) is absent: it adds nothing and is not
+   counted; count[g][.][j] is the number of homes behind curve[g][.][j].
+   The summation order is part of the contract: partial p[w], w = 0 .. DRAGG_PLAN_WAYS - 1, starts at +0.0 and
+   adds the present values of homes i = w, w + 16, w + 32, ... in ascending order with plain fp64 adds; the sum
+   is the balanced tree over the 16 partials, p[2m] + p[2m + 1] level by level: ((p0 + p1) + (p2 + p3)) + ...
+   The order depends on Nb alone, never on G or the launch: group g's rows equal those of a batch of its Nb
+   homes, bit for bit.  stats sums the present values of a vals row in the same order; min and max run over
+   them (the sign of a zero min or max is unspecified); none present: count 0, sum +0.0, min +inf, max -inf.
+   n_homes == 0: every group gets that empty result (curve +0.0, count 0).  One kernel; vector stores, no
+   atomics.  DRAGG_E_ARG: a NULL dims, hash or plan; a key bit at or past DRAGG_NFC or a row bit at or past
+   DRAGG_NVAL; horizon < 1; n_homes % G != 0 or G > 65535 (a grid row per group); curve or count NULL with
+   fc_keys != 0, stats NULL with val_rows != 0 (an output whose mask is zero may be NULL and is not written);
+   with n_homes > 0 a NULL hash.vals, or a NULL hash.fc with fc_keys != 0. */
+#define DRAGG_PLAN_WAYS 16
+typedef struct dragg_mpc_plan {
+    uint32_t fc_keys;   /* bit k < DRAGG_NFC: the horizon curve of forecast key k            */
+    uint32_t val_rows;  /* bit r < DRAGG_NVAL: statistics of vals row r                      */
+    double*  curve;     /* [G][nk][H] sums; nk = popcount(fc_keys), keys in ascending order  */
+    int32_t* count;     /* [G][nk][H] homes that contributed to each sum                     */
+    double*  stats;     /* [G][nr][4]: count, sum, min, max; nr = popcount(val_rows)         */
+} dragg_mpc_plan;
+int dragg_mpc_plan_groups(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, const dragg_mpc_plan* plan,
+                          void* stream);
+
 /* Lag mode (since v8): run_rbo_mpc's timestep loop (aggregator.py:757-778) has no feedback between
    homes, so a home whose chain needs the slow exact step-function DP need not hold up the others.
    A step is split into two passes the caller puts on two streams:
