@@ -5025,93 +5025,118 @@ __global__ __launch_bounds__(AGG_NT) void aggregate_groups_kernel(const double* 
     agg_sums(vals, N, (int)blockIdx.x * Nb, Nb, out + (size_t)blockIdx.x * 3);
 }
 
-// Fan a base batch's hash arrays out to the G replicas of a grouped batch (dragg_mpc_replicate).  Both
-// arrays are a segment of `rows` rows of R doubles whose row r goes to rows r * G + g (g < G) of the
-// destination: vals is NVAL rows of Nb (dst [NVAL][G][Nb]), fc one row of Nb * NFC * H (dst
-// [G][Nb * NFC * H]).  A thread reads one unit of the source once and stores it G times, lanes on
-// consecutive units (coalesced both ways).  A unit is 16 bytes where every row offset is (R even, both
-// bases 16-byte aligned: then g * R is even for every g), else 8 bytes -- replica offsets g * Nb are
-// not 16-byte aligned in general, and an odd Nb leaves vals no wider access that is aligned in every
-// replica.  The bits move through integer registers: NaN payloads arrive as they are.
-struct RepSeg {
-    const double* src;
-    double* dst;
-    long long R;           // doubles per row
-    long long units;       // units of the whole segment (rows * R doubles / the unit's)
-    int rows;
-    int wide;              // 1: 16-byte units
-};
-template <typename T>
-DEV void rep_copy(const RepSeg& s, long long u, int G) {
-    const long long Ru = s.R / (long long)(sizeof(T) / 8);              // units per row
-    const long long r = s.rows == 1 ? 0 : u / Ru, i = u - r * Ru;
-    const T v = reinterpret_cast<const T*>(s.src)[u];
-    T* d = reinterpret_cast<T*>(s.dst) + r * G * Ru + i;
-    for (int g = 0; g < G; ++g, d += Ru) *d = v;
-}
-constexpr int REP_NT = 256;
-constexpr int REP_BLOCKS_MAX = 4096;        // (16 per CU: a grid-stride loop over the units past that)
-__global__ __launch_bounds__(REP_NT) void replicate_kernel(RepSeg a, RepSeg b, int G) {
-    const long long n = a.units + b.units;
-    for (long long e = (long long)blockIdx.x * REP_NT + threadIdx.x; e < n; e += (long long)gridDim.x * REP_NT) {
-        const bool first = e < a.units;
-        const RepSeg& s = first ? a : b;
-        const long long u = first ? e : e - a.units;
-        if (s.wide) rep_copy<uint4>(s, u, G);
-        else rep_copy<unsigned long long>(s, u, G);
-    }
-}
-
-// The way back (dragg_mpc_adopt): the destination batch's E groups of Nb homes each take, from a source
-// that holds C copies of the destination (copy-major: replicate_kernel's layout with G = C), the columns
-// of copy choice[e].  Every array is a segment: `rows` rows whose columns are `elem` bytes wide (vals / hist:
-// NVAL rows of 8, obj / relax_obj: one row of 8, status / iters / int_path: one row of 4, fc: one row of
-// NFC * H * 8 -- a home's block).  Group e's part of a row is Nb * elem bytes at column e * Nb of the
-// destination and column c * Nd + e * Nb of the source (Nd = E * Nb).  A unit is the widest of 16 / 8 / 4
-// bytes that divides both bases, Nb * elem and Nd * elem (then every group's offset in every copy and
-// both row strides are aligned).  Block (x, e) works on group e alone, so choice[e] is block-uniform: a
-// choice outside [0, C) ends the block before any access.  Lanes on consecutive units; the bits move
-// through integer registers.
-constexpr int ADOPT_NSEG = 8;
-struct AdoptSeg {
-    const char* src;
+// The grouped segment mover: replicate, adopt, env file and env reset all move (or fill) per-group columns of a
+// batch's arrays, and differ only in which group goes where.  Every array is a SEGMENT (Seg): `rows` rows,
+// src_stride / dst_stride bytes apart, of which one group owns `group_bytes` contiguous bytes -- Nb columns of
+// 4 or 8 bytes (vals / hist: NVAL rows; obj, relax_obj, status, iters, int_path: one row), Nb homes' fc blocks
+// of NFC * H * 8 bytes (one row), or the 3 sums.  Where a group's bytes lie in a row is the kernel's own rule
+// (its functor: a byte offset per side).  A UNIT is the widest of 16 / 8 / 4 bytes that divides both bases,
+// group_bytes and both row strides (seg_add), so that every group's part of every row is aligned to it -- group
+// offsets g * Nb * 8 are not 16-byte aligned in general.  A group's work is the units of all its segments in a
+// row (Seg::end: the running total); seg_walk grid-strides over them along x, lanes on consecutive units
+// (coalesced both ways), and hands each to the functor as (segment, row, unit in the row, unit type).  The
+// bits move through integer registers: NaN payloads arrive as they are.  No LDS, no atomics.
+// The keyed kernels run on a grid (chunks, G): block (x, g) works on group g alone, reads g's key once through
+// readfirstlane, and returns BEFORE ANY ACCESS to the arrays when the key says idle.
+struct Seg {
+    const char* src;                    // (reset: unused)
     char* dst;
     long long src_stride, dst_stride;   // bytes between rows
-    long long elem;                     // bytes per column
-    long long row_units;                // units of one group's part of a row (Nb * elem / the unit's bytes)
+    long long group_bytes;
+    long long row_units;                // units of one group's part of a row
     long long end;                      // units of this and every earlier segment, per group
+    unsigned long long fill;            // reset: the 8 bytes stored (NaN as torch.full stores it, or 0)
     int unit;                           // bytes: 16, 8 or 4
     int rows;
 };
-struct AdoptArgs {
-    AdoptSeg seg[ADOPT_NSEG];
+constexpr int SEGS_MAX = 8;
+struct Segs {
+    Seg seg[SEGS_MAX];
     int nseg;
-    int copies;
-    long long Nb, Nd;
+};
+constexpr int REP_NT = 256;
+constexpr int REP_BLOCKS_MAX = 4096;        // (16 per CU: a grid-stride loop over the units past that)
+template <typename T>
+DEV T* seg_at(char* base, long long offset, long long i) { return reinterpret_cast<T*>(base + offset) + i; }
+template <typename T>
+DEV const T* seg_at(const char* base, long long offset, long long i) {
+    return reinterpret_cast<const T*>(base + offset) + i;
+}
+// f(s, r, i, T{}): unit i of the group's part of row r of segment s, T the unit's type
+template <typename F>
+DEV void seg_walk(const Segs& a, F f) {
+    const long long n = a.nseg ? a.seg[a.nseg - 1].end : 0;
+    for (long long x = (long long)blockIdx.x * REP_NT + threadIdx.x; x < n; x += (long long)gridDim.x * REP_NT) {
+        int k = 0;
+        while (x >= a.seg[k].end) ++k;
+        const Seg s = a.seg[k];     // (k varies by lane: a copy is one round of wide loads, a reference three narrow)
+        const long long u = x - (k ? a.seg[k - 1].end : 0);
+        const long long r = s.rows == 1 ? 0 : u / s.row_units, i = u - r * s.row_units;
+        if (s.unit == 16) f(s, r, i, uint4{});
+        else if (s.unit == 8) f(s, r, i, 0ull);
+        else f(s, r, i, 0u);
+    }
+}
+// host: one segment more, with the unit rule.  false: a base or a stride that is not a multiple of the element
+// size `elem` (4 or 8), or no room
+bool seg_add(Segs& a, const void* src, void* dst, long long src_stride, long long dst_stride, long long group_bytes,
+             int rows, long long elem, unsigned long long fill = 0) {
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) |
+                           (uintptr_t)group_bytes | (uintptr_t)src_stride | (uintptr_t)dst_stride;
+    if (bits % elem != 0 || a.nseg == SEGS_MAX) return false;
+    const int unit = bits % 16 == 0 ? 16 : bits % 8 == 0 ? 8 : 4;
+    const long long row_units = group_bytes / unit;
+    a.seg[a.nseg] = Seg{static_cast<const char*>(src), static_cast<char*>(dst), src_stride, dst_stride, group_bytes,
+                        row_units, (a.nseg ? a.seg[a.nseg - 1].end : 0) + rows * row_units, fill, unit, rows};
+    ++a.nseg;
+    return true;
+}
+// host: the launch on the grid (chunks, G), chunks capped so that the grid holds REP_BLOCKS_MAX blocks at the
+// most (G = 1: the one-dimensional form).  A grid has a row per group: G <= 65535
+template <typename Args>
+int seg_launch(void (*kernel)(Args), const Args& a, int G, void* stream) {
+    if (G < 1 || G > 65535) return DRAGG_E_ARG;
+    const long long units = a.segs.nseg ? a.segs.seg[a.segs.nseg - 1].end : 0;
+    const long long blocks = max(1LL, (units + REP_NT - 1) / REP_NT);
+    const long long cap = max(1LL, (long long)REP_BLOCKS_MAX / G);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)min(blocks, cap), (unsigned)G), dim3(REP_NT), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+}
+
+// dragg_mpc_replicate: the base batch is the one group of the source, and its part of row r goes to every group
+// g < G of the destination's row (vals: NVAL rows of Nb -> [NVAL][G][Nb]; fc: one row of Nb * NFC * H ->
+// [G][Nb * NFC * H]).  One-dimensional grid, no key: a thread reads a unit once and stores it G times.
+struct ReplicateArgs {
+    Segs segs;
+    int G;
+};
+__global__ __launch_bounds__(REP_NT) void replicate_kernel(ReplicateArgs a) {
+    seg_walk(a.segs, [&](const Seg& s, long long r, long long i, auto unit) {
+        using T = decltype(unit);
+        const T v = *seg_at<T>(s.src, r * s.src_stride, i);
+        T* d = seg_at<T>(s.dst, r * s.dst_stride, i);
+        for (int g = 0; g < a.G; ++g, d += s.row_units) *d = v;
+    });
+}
+
+// dragg_mpc_adopt, the way back: the source holds C copies of the destination's E groups, copy-major
+// (replicate's layout with G = C), so group e takes the bytes of the source's group choice[e] * E + e.  A
+// choice outside [0, C) is idle.
+struct AdoptArgs {
+    Segs segs;
+    int copies, E;
     const int32_t* choice;
 };
-template <typename T>
-DEV void adopt_copy(const AdoptSeg& s, long long u, long long src_col, long long dst_col) {
-    const long long r = s.rows == 1 ? 0 : u / s.row_units, i = u - r * s.row_units;
-    const T* p = reinterpret_cast<const T*>(s.src + r * s.src_stride + src_col * s.elem) + i;
-    T* q = reinterpret_cast<T*>(s.dst + r * s.dst_stride + dst_col * s.elem) + i;
-    *q = *p;
-}
 __global__ __launch_bounds__(REP_NT) void adopt_kernel(AdoptArgs a) {
     const int e = (int)blockIdx.y;
     const int c = __builtin_amdgcn_readfirstlane(a.choice[e]);
     if (c < 0 || c >= a.copies) return;
-    const long long dst_col = (long long)e * a.Nb, src_col = (long long)c * a.Nd + dst_col;
-    const long long n = a.seg[a.nseg - 1].end;
-    for (long long x = (long long)blockIdx.x * REP_NT + threadIdx.x; x < n; x += (long long)gridDim.x * REP_NT) {
-        int k = 0;
-        while (x >= a.seg[k].end) ++k;
-        const AdoptSeg& s = a.seg[k];
-        const long long u = x - (k ? a.seg[k - 1].end : 0);
-        if (s.unit == 16) adopt_copy<uint4>(s, u, src_col, dst_col);
-        else if (s.unit == 8) adopt_copy<unsigned long long>(s, u, src_col, dst_col);
-        else adopt_copy<unsigned>(s, u, src_col, dst_col);
-    }
+    const long long from = (long long)c * a.E + e;
+    seg_walk(a.segs, [&](const Seg& s, long long r, long long i, auto unit) {
+        using T = decltype(unit);
+        *seg_at<T>(s.dst, r * s.dst_stride + e * s.group_bytes, i) =
+            *seg_at<T>(s.src, r * s.src_stride + from * s.group_bytes, i);
+    });
 }
 
 // dragg_mpc_select_groups: lane e picks, for group e, the copy whose load (sums[c * E + e][0]) lies closest
@@ -5135,28 +5160,10 @@ __global__ void select_groups_kernel(int E, int C, const double* sums, const dou
 }
 
 // The device-resident vector environment (dragg_mpc_env_file, dragg_mpc_env_reset): what the host does around
-// a step of E episodes, as one launch each, in adopt_kernel's shape -- grid (chunks, G), block (x, g) works on
-// group g alone, its key (the timestep the group ran with / its mask byte) read once per block through
-// readfirstlane, so an idle group's blocks return before any access.  Every array is a segment of `rows` rows;
-// group g's part of a row is `group_bytes` bytes at byte g * group_bytes of the row (Nb columns of 4 or 8 bytes;
-// a home's fc block; the 3 sums).  A unit is the widest of 16 / 8 / 4 bytes that divides every base, group_bytes
-// and every stride.  Lanes on consecutive units; the bits move through integer registers.  No LDS, no atomics.
-constexpr int ENV_NSEG = 6;
-struct EnvSeg {
-    const char* src;                    // file: the step's row(s); reset: unused
-    char* dst;
-    long long src_stride, dst_stride;   // bytes between rows
-    long long t_stride;                 // file: bytes between the timesteps of the store
-    long long group_bytes;
-    long long row_units;                // units of one group's part of a row
-    long long end;                      // units of this and every earlier segment, per group
-    unsigned long long fill;            // reset: the 8 bytes stored (NaN as torch.full stores it, or 0)
-    int unit;                           // bytes: 16, 8 or 4
-    int rows;
-};
+// a step of E episodes, as one launch each over the mover's segments, plus the setpoint state of the group (one
+// lane of its first block).  Keys: the timestep the group ran with (file) / its mask byte (reset).
 struct EnvArgs {
-    EnvSeg seg[ENV_NSEG];
-    int nseg;
+    Segs segs;
     int G, T, P;
     double fresh_load;                  // 0.5 * max_poss_load: every tracked load of a fresh episode
     double start_load;
@@ -5216,52 +5223,39 @@ DEV void env_setpoint(const EnvArgs& a, int g, int timestep, double load, double
     a.obs[4 * G + g] = (double)timestep;
 }
 
-template <typename T>
-DEV void env_copy(const EnvSeg& s, long long u, long long g, long long t) {
-    const long long r = s.rows == 1 ? 0 : u / s.row_units, i = u - r * s.row_units;
-    const T* p = reinterpret_cast<const T*>(s.src + r * s.src_stride + g * s.group_bytes) + i;
-    T* q = reinterpret_cast<T*>(s.dst + t * s.t_stride + r * s.dst_stride + g * s.group_bytes) + i;
-    *q = *p;
-}
+// file: group g's part of the step's row(s) goes to timestep t = ran[g] of the store, whose timesteps lie
+// `rows` destination rows apart.  ran[g] outside [0, T) is idle.
 __global__ __launch_bounds__(REP_NT) void env_file_kernel(EnvArgs a) {
     const int g = (int)blockIdx.y;
     const int t = __builtin_amdgcn_readfirstlane(a.ran[g]);
     if (t < 0 || t >= a.T) return;
-    const long long n = a.nseg ? a.seg[a.nseg - 1].end : 0;
-    for (long long x = (long long)blockIdx.x * REP_NT + threadIdx.x; x < n; x += (long long)gridDim.x * REP_NT) {
-        int k = 0;
-        while (x >= a.seg[k].end) ++k;
-        const EnvSeg& s = a.seg[k];
-        const long long u = x - (k ? a.seg[k - 1].end : 0);
-        if (s.unit == 16) env_copy<uint4>(s, u, g, t);
-        else if (s.unit == 8) env_copy<unsigned long long>(s, u, g, t);
-        else env_copy<unsigned>(s, u, g, t);
-    }
+    seg_walk(a.segs, [&](const Seg& s, long long r, long long i, auto unit) {
+        using T = decltype(unit);
+        *seg_at<T>(s.dst, ((long long)t * s.rows + r) * s.dst_stride + g * s.group_bytes, i) =
+            *seg_at<T>(s.src, r * s.src_stride + g * s.group_bytes, i);
+    });
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         const double* s3 = a.sums + (size_t)g * 3;
         env_setpoint(a, g, t + 1, s3[0], s3[1], s3[2], t + 1 < 2);
     }
 }
 
-template <typename T>
-DEV void env_fill(const EnvSeg& s, long long u, long long g, T v) {
-    const long long r = s.rows == 1 ? 0 : u / s.row_units, i = u - r * s.row_units;
-    reinterpret_cast<T*>(s.dst + r * s.dst_stride + g * s.group_bytes)[i] = v;
-}
+// reset: group g's part of every row takes the segment's `fill` (4-byte units: the int32 stores, filled with
+// its low half, 0).  A mask byte of 0 is idle.
 __global__ __launch_bounds__(REP_NT) void env_reset_kernel(EnvArgs a) {
     const int g = (int)blockIdx.y;
     if (!__builtin_amdgcn_readfirstlane((int)a.mask[g])) return;
-    const long long n = a.nseg ? a.seg[a.nseg - 1].end : 0;
-    for (long long x = (long long)blockIdx.x * REP_NT + threadIdx.x; x < n; x += (long long)gridDim.x * REP_NT) {
-        int k = 0;
-        while (x >= a.seg[k].end) ++k;
-        const EnvSeg& s = a.seg[k];
-        const long long u = x - (k ? a.seg[k - 1].end : 0);
-        const unsigned lo = (unsigned)s.fill, hi = (unsigned)(s.fill >> 32);
-        if (s.unit == 16) env_fill<uint4>(s, u, g, uint4{lo, hi, lo, hi});
-        else if (s.unit == 8) env_fill<unsigned long long>(s, u, g, s.fill);
-        else env_fill<unsigned>(s, u, g, lo);        // (4-byte units: the int32 stores, filled with 0)
-    }
+    seg_walk(a.segs, [&](const Seg& s, long long r, long long i, auto unit) {
+        using T = decltype(unit);
+        T v;
+        if constexpr (sizeof(T) == 16) {
+            const unsigned lo = (unsigned)s.fill, hi = (unsigned)(s.fill >> 32);
+            v = uint4{lo, hi, lo, hi};
+        } else {
+            v = (T)s.fill;
+        }
+        *seg_at<T>(s.dst, r * s.dst_stride + g * s.group_bytes, i) = v;
+    });
     if (blockIdx.x == 0 && threadIdx.x == 0) env_setpoint(a, g, 0, a.start_load, a.start_load, 0.0, true);
 }
 
@@ -5927,16 +5921,14 @@ int dragg_mpc_replicate(const dragg_mpc_dims* dims, const dragg_mpc_hash* src_ha
     if (dims->n_homes == 0) return DRAGG_OK;
     if (!src_hash->vals || !src_hash->fc || !dst_hash->vals || !dst_hash->fc) return DRAGG_E_ARG;
     const long long Nb = dims->n_homes / G;
-    auto seg = [&](const double* s, double* d, long long R, int rows) {
-        const bool wide = R % 2 == 0 && (reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d)) % 16 == 0;
-        return RepSeg{s, d, R, rows * R / (wide ? 2 : 1), rows, wide ? 1 : 0};
+    ReplicateArgs a{};
+    a.G = G;
+    auto seg = [&](const double* s, double* d, long long R, int rows) {       // rows of R doubles -> rows of G * R
+        return seg_add(a.segs, s, d, R * 8, G * R * 8, R * 8, rows, 8);
     };
-    const RepSeg v = seg(src_hash->vals, dst_hash->vals, Nb, DRAGG_NVAL);
-    const RepSeg f = seg(src_hash->fc, dst_hash->fc, Nb * DRAGG_NFC * dims->horizon, 1);
-    const long long blocks = (v.units + f.units + REP_NT - 1) / REP_NT;
-    hipLaunchKernelGGL(replicate_kernel, dim3((unsigned)min(blocks, (long long)REP_BLOCKS_MAX)), dim3(REP_NT), 0,
-                       (hipStream_t)stream, v, f, G);
-    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+    if (!seg(src_hash->vals, dst_hash->vals, Nb, DRAGG_NVAL) ||
+        !seg(src_hash->fc, dst_hash->fc, Nb * DRAGG_NFC * dims->horizon, 1)) return DRAGG_E_ARG;
+    return seg_launch(replicate_kernel, a, 1, stream);
 }
 
 int dragg_mpc_adopt(const dragg_mpc_dims* dst_dims, int32_t copies, const int32_t* choice,
@@ -5951,35 +5943,24 @@ int dragg_mpc_adopt(const dragg_mpc_dims* dst_dims, int32_t copies, const int32_
     const long long Nd = dst_dims->n_homes, Nb = Nd / E;
     AdoptArgs a{};
     a.copies = copies;
-    a.Nb = Nb;
-    a.Nd = Nd;
+    a.E = E;
     a.choice = choice;
-    auto seg = [&](const void* s, void* d, long long elem, int rows) {
-        if (!s || !d) return;              // a member either side leaves out
-        const uintptr_t bits = reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d) |
-                               (uintptr_t)(Nb * elem) | (uintptr_t)(Nd * elem);
-        const int unit = bits % 16 == 0 ? 16 : bits % 8 == 0 ? 8 : 4;
-        AdoptSeg& g = a.seg[a.nseg];
-        g = AdoptSeg{static_cast<const char*>(s), static_cast<char*>(d), (long long)copies * Nd * elem, Nd * elem,
-                     elem, Nb * elem / unit, 0, unit, rows};
-        g.end = (a.nseg ? a.seg[a.nseg - 1].end : 0) + rows * g.row_units;
-        ++a.nseg;
+    bool ok = true;
+    // rows of Nd columns of `col` bytes (the source's: C * Nd); a member either side leaves out is not moved
+    auto seg = [&](const void* s, void* d, long long col, int rows, long long elem) {
+        if (s && d) ok = seg_add(a.segs, s, d, copies * Nd * col, Nd * col, Nb * col, rows, elem) && ok;
     };
-    seg(src_hash->fc, dst_hash->fc, (long long)DRAGG_NFC * dst_dims->horizon * 8, 1);
-    seg(src_hash->vals, dst_hash->vals, 8, DRAGG_NVAL);
+    seg(src_hash->fc, dst_hash->fc, (long long)DRAGG_NFC * dst_dims->horizon * 8, 1, 8);
+    seg(src_hash->vals, dst_hash->vals, 8, DRAGG_NVAL, 8);
     if (src_out && dst_out) {
-        seg(src_out->hist, dst_out->hist, 8, DRAGG_NVAL);
-        seg(src_out->obj, dst_out->obj, 8, 1);
-        seg(src_out->relax_obj, dst_out->relax_obj, 8, 1);
-        seg(src_out->status, dst_out->status, 4, 1);
-        seg(src_out->iters, dst_out->iters, 4, 1);
-        seg(src_out->int_path, dst_out->int_path, 4, 1);
+        seg(src_out->hist, dst_out->hist, 8, DRAGG_NVAL, 8);
+        seg(src_out->obj, dst_out->obj, 8, 1, 8);
+        seg(src_out->relax_obj, dst_out->relax_obj, 8, 1, 8);
+        seg(src_out->status, dst_out->status, 4, 1, 4);
+        seg(src_out->iters, dst_out->iters, 4, 1, 4);
+        seg(src_out->int_path, dst_out->int_path, 4, 1, 4);
     }
-    const long long blocks = (a.seg[a.nseg - 1].end + REP_NT - 1) / REP_NT;
-    const long long cap = max(1LL, (long long)REP_BLOCKS_MAX / E);
-    hipLaunchKernelGGL(adopt_kernel, dim3((unsigned)min(blocks, cap), (unsigned)E), dim3(REP_NT), 0,
-                       (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+    return ok ? seg_launch(adopt_kernel, a, E, stream) : DRAGG_E_ARG;
 }
 
 int dragg_mpc_select_groups(const dragg_mpc_dims* dst_dims, int32_t copies, const double* sums, const double* target,
@@ -6023,29 +6004,10 @@ static int env_args(const dragg_mpc_dims* dims, const dragg_mpc_env* env, EnvArg
     return G;
 }
 
-// one segment more: `rows` rows of which group g owns group_bytes bytes at byte g * group_bytes (row strides
-// G * group_bytes; the store's timesteps rows * that apart).  false: an address not aligned to its elements
+// one segment more: `rows` rows of the G groups' parts side by side, both sides alike
 static bool env_seg(EnvArgs& a, const void* src, void* dst, long long group_bytes, int rows, long long elem,
                     unsigned long long fill) {
-    const long long stride = a.G * group_bytes;
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) |
-                           (uintptr_t)group_bytes | (uintptr_t)stride;
-    if (bits % elem != 0) return false;
-    const int unit = bits % 16 == 0 ? 16 : bits % 8 == 0 ? 8 : 4;
-    EnvSeg& s = a.seg[a.nseg];
-    s = EnvSeg{static_cast<const char*>(src), static_cast<char*>(dst), stride, stride, rows * stride, group_bytes,
-               group_bytes / unit, 0, fill, unit, rows};
-    s.end = (a.nseg ? a.seg[a.nseg - 1].end : 0) + rows * s.row_units;
-    ++a.nseg;
-    return true;
-}
-
-static int env_launch(void (*kernel)(EnvArgs), const EnvArgs& a, void* stream) {
-    const long long units = a.nseg ? a.seg[a.nseg - 1].end : 0;
-    const long long blocks = max(1LL, (units + REP_NT - 1) / REP_NT);
-    const long long cap = max(1LL, (long long)REP_BLOCKS_MAX / a.G);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)min(blocks, cap), (unsigned)a.G), dim3(REP_NT), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+    return seg_add(a.segs, src, dst, a.G * group_bytes, a.G * group_bytes, group_bytes, rows, elem, fill);
 }
 
 int dragg_mpc_env_file(const dragg_mpc_dims* dims, const dragg_mpc_env* env, const dragg_mpc_out* out, void* stream) {
@@ -6069,7 +6031,7 @@ int dragg_mpc_env_file(const dragg_mpc_dims* dims, const dragg_mpc_env* env, con
     if (path) ok = ok && env_seg(a, path, env->path_hist, Nb * 4, 1, 4, 0);
     if (env->agg_hist) ok = ok && env_seg(a, env->sums, env->agg_hist, 3 * 8, 1, 8, 0);
     if (!ok) return DRAGG_E_ARG;
-    return env_launch(env_file_kernel, a, stream);
+    return seg_launch(env_file_kernel, a, G, stream);
 }
 
 int dragg_mpc_env_reset(const dragg_mpc_dims* dims, const dragg_mpc_env* env, const uint8_t* mask,
@@ -6091,7 +6053,7 @@ int dragg_mpc_env_reset(const dragg_mpc_dims* dims, const dragg_mpc_env* env, co
     if (env->path_hist) ok = ok && env_seg(a, nullptr, env->path_hist, Nb * 4, T, 4, 0);
     if (env->agg_hist) ok = ok && env_seg(a, nullptr, env->agg_hist, 3 * 8, T, 8, 0);
     if (!ok) return DRAGG_E_ARG;
-    return env_launch(env_reset_kernel, a, stream);
+    return seg_launch(env_reset_kernel, a, G, stream);
 }
 
 int dragg_mpc_plan_groups(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, const dragg_mpc_plan* plan,

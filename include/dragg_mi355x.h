@@ -331,7 +331,8 @@ int dragg_mpc_aggregate(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, 
    [DRAGG_NVAL][Nb] and fc [Nb][DRAGG_NFC][H], dst_hash the grouped batch's vals [DRAGG_NVAL][G * Nb] and
    fc [G * Nb][DRAGG_NFC][H].  Every replica receives its base home's fields bit for bit (NaN payloads
    included: NaN = field absent).  One kernel: each source element is read once and stored G times.
-   src_hash is only read. */
+   src_hash is only read.  DRAGG_E_ARG also for a vals or fc pointer, on either side, that is not a multiple
+   of 8 (before the grouped segment mover such a pointer was undefined behaviour); nothing is written then. */
 int dragg_mpc_replicate(const dragg_mpc_dims* dims, const dragg_mpc_hash* src_hash,
                         dragg_mpc_hash* dst_hash, void* stream);
 
@@ -346,7 +347,9 @@ int dragg_mpc_replicate(const dragg_mpc_dims* dims, const dragg_mpc_hash* src_ha
    [0, C) leaves every column of group e untouched -- no byte of it is written: idle or parked episodes and
    "no valid candidate" pass through.  Bit for bit (NaN payloads included: NaN = field absent); src_* is
    only read.  One kernel; a block works on one group, so the choice is read once per block.  n_homes == 0:
-   a no-op.  DRAGG_E_ARG: copies < 1, n_homes % E != 0, E > 65535, a NULL choice or NULL hash pointers. */
+   a no-op.  DRAGG_E_ARG: copies < 1, n_homes % E != 0, E > 65535, a NULL choice or NULL hash pointers, or an
+   array pointer that is not a multiple of its element size (8 for the double arrays, 4 for status, iters and
+   int_path; before the grouped segment mover such a pointer was undefined behaviour); nothing is written then. */
 int dragg_mpc_adopt(const dragg_mpc_dims* dst_dims, int32_t copies, const int32_t* choice,
                     const dragg_mpc_hash* src_hash, const dragg_mpc_out* src_out,
                     dragg_mpc_hash* dst_hash, dragg_mpc_out* dst_out, void* stream);

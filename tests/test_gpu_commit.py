@@ -152,6 +152,111 @@ def test_adopt_arguments(gpu):
     assert _same(dst, want)
 
 
+# raw pointers at chosen byte offsets (tests/arena.py): every unit width, the one-block-per-group loop, the refusal
+ADOPT_F64, ADOPT_I32 = ("vals", "fc", "hist", "obj", "relax_obj"), ("status", "iters", "int_path")
+
+
+def _adopt_arena(L, Nb, E, C, H, offs):
+    from tests.arena import Arena
+    ar = Arena()
+    for side, n, (f8, i4) in (("src_", C * Nb * E, offs[0::2]), ("dst_", Nb * E, offs[1::2])):
+        for k in ADOPT_F64:
+            ar.add(side + k, np.float64, {"vals": (L.NVAL, n), "hist": (L.NVAL, n), "fc": (n, L.NFC, H)}.get(k, (n,)), f8)
+        for k in ADOPT_I32:
+            ar.add(side + k, np.int32, (n,), i4)
+    return ar
+
+
+def _adopt_rule(ar, src_buf, dst_buf, choice, Nb, E, C):
+    """The index rule on the host bytes: group e's Nb columns of every row (fc: its Nb homes' blocks) from columns
+    [c * Nd + e * Nb, ...) of the source, c = choice[e] in [0, C); any other group: nothing."""
+    Nd = Nb * E
+    for e, c in enumerate(choice):
+        if not 0 <= c < C:
+            continue
+        d, s = slice(e * Nb, (e + 1) * Nb), slice(c * Nd + e * Nb, c * Nd + (e + 1) * Nb)
+        for k in ADOPT_F64 + ADOPT_I32:
+            src, dst = ar.view(src_buf, "src_" + k), ar.view(dst_buf, "dst_" + k)
+            if k == "fc":
+                dst[d] = src[s]
+            else:
+                dst[..., d] = src[..., s]
+
+
+def _adopt_raw(L, lib, ar, dev, Nb, E, C, H, choice, gpu):
+    ch = torch.tensor(choice, dtype=torch.int32, device=gpu)
+    p = lambda k: ar.ptr(dev, k)  # noqa: E731
+    structs = []
+    for side in ("src_", "dst_"):
+        structs += [L.Hash(vals=p(side + "vals"), fc=p(side + "fc")),
+                    L.Out(status=p(side + "status"), iters=p(side + "iters"), obj=p(side + "obj"),
+                          relax_obj=p(side + "relax_obj"), hist=p(side + "hist"), cycles=None,
+                          int_path=p(side + "int_path"))]
+    dims = L.Dims(n_homes=Nb * E, horizon=H, sub_steps=6, dt=1, n_groups=E if E > 1 else 0)
+    rc = lib.dragg_mpc_adopt(dims, C, L.ptr(ch), structs[0], structs[1], structs[2], structs[3], L.stream_ptr(None, gpu))
+    torch.cuda.synchronize()
+    return rc
+
+
+@pytest.mark.parametrize("Nb", [1, 3, 4])
+@pytest.mark.parametrize("E", [1, 3])
+def test_adopt_every_unit_width(gpu, Nb, E):
+    """Bases 0 / 8 (doubles) and 0 / 4 / 8 / 12 (int32) bytes past a 16-byte boundary: by the unit rule the
+    double rows move in 16-byte units at Nb = 4 with both bases aligned and in 8-byte units otherwise, the int32
+    rows in 16-, 8- and 4-byte units (Nb = 4 at offsets 0 / 8 / 4 and 12; Nb odd: 4), fc in 16-byte units at
+    Nb = 4 and in 8-byte units otherwise.  Every byte of the allocation is compared, the idle groups', the
+    source's and the guards' included."""
+    from dragg_amd import _lib as L
+    from tests.arena import OFFSETS, same_bytes
+    lib, C, H = L.load(), 2, 3
+    rng = np.random.default_rng(10 * Nb + E)
+    for offs in OFFSETS:
+        ar = _adopt_arena(L, Nb, E, C, H, offs)
+        for choice in (([1, -1, 0], [2, 0, 1]) if E == 3 else ([1], [-1])):
+            h0 = ar.random(rng)
+            want = h0.copy()
+            _adopt_rule(ar, h0, want, choice, Nb, E, C)
+            dev = ar.upload(h0, gpu)
+            assert _adopt_raw(L, lib, ar, dev, Nb, E, C, H, choice, gpu) == 0
+            assert same_bytes(dev.cpu().numpy(), want, ar), (offs, choice)
+            for e, c in enumerate(choice):                       # (the restatement left the idle groups alone)
+                if not 0 <= c < C:
+                    assert np.array_equal(ar.view(want, "dst_vals")[:, e * Nb:(e + 1) * Nb].view(np.int64),
+                                          ar.view(h0, "dst_vals")[:, e * Nb:(e + 1) * Nb].view(np.int64))
+
+
+def test_adopt_one_block_per_group(gpu):
+    """E = 5,000 groups of 3 homes, H = 24, about half of them idle: the grid is one block per group, and a
+    block walks its group's ~1,200 units (8-byte units: the doubles lie 8 bytes past a 16-byte boundary) over
+    all eight segments in its stride loop."""
+    from dragg_amd import _lib as L
+    from tests.arena import same_bytes
+    lib, Nb, E, C, H = L.load(), 3, 5000, 2, 24
+    rng = np.random.default_rng(7)
+    choice = rng.integers(-1, C + 1, E).tolist()                 # (-1 and C: idle)
+    assert 0.4 * E < sum(0 <= c < C for c in choice) < 0.6 * E
+    ar = _adopt_arena(L, Nb, E, C, H, (8, 8, 0, 0))
+    h0 = ar.random(rng)
+    want = h0.copy()
+    _adopt_rule(ar, h0, want, choice, Nb, E, C)
+    dev = ar.upload(h0, gpu)
+    assert _adopt_raw(L, lib, ar, dev, Nb, E, C, H, choice, gpu) == 0
+    assert same_bytes(dev.cpu().numpy(), want, ar)
+
+
+def test_adopt_refuses_a_misaligned_double_array(gpu):
+    """A double array 4 bytes past an 8-byte boundary: DRAGG_E_ARG, and no byte is written."""
+    from dragg_amd import _lib as L
+    lib, Nb, E, C, H = L.load(), 3, 2, 2, 3
+    rng = np.random.default_rng(3)
+    for offs in ((4, 0, 0, 0), (0, 4, 0, 0), (12, 12, 0, 0)):
+        ar = _adopt_arena(L, Nb, E, C, H, offs)
+        h0 = ar.random(rng)
+        dev = ar.upload(h0, gpu)
+        assert _adopt_raw(L, lib, ar, dev, Nb, E, C, H, [1, 0], gpu) == -1, offs
+        assert np.array_equal(dev.cpu().numpy(), h0), offs
+
+
 def test_adopt_from_checks_its_arguments(gpu):
     from dragg_amd.community import synthetic_homes, synthetic_weather
     from dragg_amd.mpc import MPCBatch

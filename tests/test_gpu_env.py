@@ -180,6 +180,145 @@ def test_env_entry_points_refuse_bad_arguments(gpu, community):
     _equal(st, ref, "nothing ran")
 
 
+# ------------------------------------------------------------------ raw pointers at chosen byte offsets
+ENV_P = 3
+
+
+def _env_arena(Nb, G, H, T, offs):
+    """Every array both entry points take (tests/arena.py): the step's sources, the stores, the hash arrays and
+    the setpoint state, the moved ones at the given offsets."""
+    from tests.arena import Arena
+    f_src, f_dst, i_src, i_dst = offs
+    N, ar = Nb * G, Arena()
+    for k in ("status", "int_path"):
+        ar.add(k, np.int32, (N,), i_src)
+    ar.add("row", np.float64, (L.NVAL, N), f_src)
+    ar.add("sums", np.float64, (G, 3), f_src)
+    for k in ("status_hist", "path_hist"):
+        ar.add(k, np.int32, (T, N), i_dst)
+    ar.add("hist", np.float64, (T, L.NVAL, N), f_dst)
+    ar.add("agg_hist", np.float64, (T, G, 3), f_dst)
+    ar.add("vals", np.float64, (L.NVAL, N), f_dst)
+    ar.add("fc", np.float64, (N, L.NFC, H), f_dst)
+    for k, dtype, shape in (("clock", np.int32, (G,)), ("ran", np.int32, (G,)), ("mask", np.uint8, (G,)),
+                            ("tracked", np.float64, (G, ENV_P)), ("max_load", np.float64, (G,)),
+                            ("min_load", np.float64, (G,)), ("obs", np.float64, (5, G))):
+        ar.add(k, dtype, shape)
+    return ar
+
+
+def _env_bytes(ar, rng, G, keys):
+    """Random bits everywhere (NaN payloads in the double arrays), ordinary numbers where the setpoint rule
+    computes (sums and the setpoint state), and the groups' keys (`ran`, or `mask`)."""
+    buf = ar.random(rng)
+    for k in ("sums", "tracked", "max_load", "min_load", "obs"):
+        v = ar.view(buf, k)
+        v[...] = rng.random(v.shape) * 40.0
+    ar.view(buf, "clock")[:] = 100 + np.arange(G)
+    ar.view(buf, "ran")[:] = keys if keys.dtype == np.int32 else -1
+    ar.view(buf, "mask")[:] = keys if keys.dtype == np.uint8 else 0
+    return buf
+
+
+def _env_raw(ar, buf, dev, Nb, G, H, T):
+    """(dims, the dragg_mpc_env of the device bytes, the reference's dict over the views of `buf`)."""
+    p = lambda k: ar.ptr(dev, k)  # noqa: E731
+    scal = dict(num_timesteps=T, prev_timesteps=ENV_P, max_poss_load=61.7, start_load=3.0 * Nb)
+    env = L.Env(ran=p("ran"), sums=p("sums"), **scal, **{k: p(k) for k in STATE})
+    dims = L.Dims(n_homes=Nb * G, horizon=H, sub_steps=6, dt=1, n_groups=G if G > 1 else 0)
+    return dims, env, {**scal, **ar.views(buf, STATE)}
+
+
+def _file_raw(gpu, Nb, G, H, T, offs, ran, rng):
+    """dragg_mpc_env_file on raw pointers -> (return code, the bytes before, after, by `env_file_reference`)."""
+    from dragg_amd.vector import env_file_reference
+    ar = _env_arena(Nb, G, H, T, offs)
+    h0 = _env_bytes(ar, rng, G, np.asarray(ran, dtype=np.int32))
+    want = h0.copy()
+    dev = ar.upload(h0, gpu)
+    dims, env, ref = _env_raw(ar, want, dev, Nb, G, H, T)
+    env_file_reference(ref, ar.view(h0, "ran"), ar.view(h0, "sums"), ar.view(h0, "status"), ar.view(h0, "int_path"),
+                       ar.view(h0, "row"))
+    out = L.Out(status=ar.ptr(dev, "status"), hist=ar.ptr(dev, "row"), int_path=ar.ptr(dev, "int_path"))
+    rc = L.load().dragg_mpc_env_file(dims, env, out, L.stream_ptr(None, gpu))
+    torch.cuda.synchronize()
+    return rc, ar, h0, dev.cpu().numpy(), want
+
+
+def _reset_raw(gpu, Nb, G, H, T, offs, mask, rng):
+    """dragg_mpc_env_reset on raw pointers -> (return code, the bytes before, after, by `env_reset_reference`)."""
+    from dragg_amd.vector import env_reset_reference
+    ar = _env_arena(Nb, G, H, T, offs)
+    h0 = _env_bytes(ar, rng, G, np.asarray(mask, dtype=np.uint8))
+    want = h0.copy()
+    dev = ar.upload(h0, gpu)
+    dims, env, ref = _env_raw(ar, want, dev, Nb, G, H, T)
+    env_reset_reference(ref, ar.view(h0, "mask"), ar.view(want, "vals"), ar.view(want, "fc"))
+    rc = L.load().dragg_mpc_env_reset(dims, env, ar.ptr(dev, "mask"), L.Hash(vals=ar.ptr(dev, "vals"), fc=ar.ptr(dev, "fc")),
+                                      L.stream_ptr(None, gpu))
+    torch.cuda.synchronize()
+    return rc, ar, h0, dev.cpu().numpy(), want
+
+
+def _idle_untouched(ar, h0, got, Nb, idle):
+    """The bytes of the idle groups' columns, as they were (beside a live group's, which changed)."""
+    for g in idle:
+        cols = slice(g * Nb, (g + 1) * Nb)
+        for k in ("status_hist", "path_hist", "hist", "vals"):
+            assert np.array_equal(ar.view(got, k)[..., cols].view(np.uint8), ar.view(h0, k)[..., cols].view(np.uint8)), (g, k)
+        assert np.array_equal(ar.view(got, "fc")[cols].view(np.uint8), ar.view(h0, "fc")[cols].view(np.uint8)), g
+        assert np.array_equal(ar.view(got, "agg_hist")[:, g].view(np.uint8), ar.view(h0, "agg_hist")[:, g].view(np.uint8)), g
+
+
+@pytest.mark.parametrize("Nb", [1, 3, 4])
+@pytest.mark.parametrize("G", [1, 3])
+def test_env_file_and_reset_every_unit_width(gpu, Nb, G):
+    """Bases 0 / 8 (doubles) and 0 / 4 / 8 / 12 (int32) bytes past a 16-byte boundary, H = 3, T = 2: by the unit
+    rule the double rows move in 16-byte units at Nb = 4 with both bases aligned and in 8-byte units otherwise
+    (the 24-byte sums: 8), the int32 rows in 16-, 8- and 4-byte units (Nb = 4 at offsets 0 / 8 / 4 and 12; Nb
+    odd: 4).  Every byte of the allocation is compared with the restatements': the idle groups', the sources'
+    and the guards' included."""
+    from tests.arena import OFFSETS, same_bytes
+    H, T = 3, 2
+    rng = np.random.default_rng(10 * Nb + G)
+    for offs in OFFSETS:
+        for ran in (([1, -1, 0], [2, 0, -5]) if G == 3 else ([1], [-1], [T])):
+            rc, ar, h0, got, want = _file_raw(gpu, Nb, G, H, T, offs, ran, rng)
+            assert rc == 0 and same_bytes(got, want, ar), ("file", offs, ran)
+            _idle_untouched(ar, h0, got, Nb, [g for g, t in enumerate(ran) if not 0 <= t < T])
+        for mask in (([1, 0, 1], [0, 255, 0]) if G == 3 else ([1], [0])):
+            rc, ar, h0, got, want = _reset_raw(gpu, Nb, G, H, T, offs, mask, rng)
+            assert rc == 0 and same_bytes(got, want, ar), ("reset", offs, mask)
+            _idle_untouched(ar, h0, got, Nb, [g for g, m in enumerate(mask) if not m])
+
+
+def test_env_file_and_reset_one_block_per_group(gpu):
+    """G = 5,000 groups of 3 homes, H = 24, T = 2, about half of them idle: the grid is one block per group, and
+    a block walks all its group's units over every segment in its stride loop (8-byte units: the doubles lie 8
+    bytes past a 16-byte boundary; the reset's ~1,200 units are five passes)."""
+    from tests.arena import same_bytes
+    Nb, G, H, T = 3, 5000, 24, 2
+    rng = np.random.default_rng(11)
+    ran = rng.integers(-1, T + 1, G).tolist()                    # (-1 and T: idle)
+    assert 0.4 * G < sum(0 <= t < T for t in ran) < 0.6 * G
+    rc, ar, h0, got, want = _file_raw(gpu, Nb, G, H, T, (8, 8, 0, 0), ran, rng)
+    assert rc == 0 and same_bytes(got, want, ar)
+    mask = (rng.random(G) < 0.5).astype(np.uint8)
+    rc, ar, h0, got, want = _reset_raw(gpu, Nb, G, H, T, (8, 8, 0, 0), mask, rng)
+    assert rc == 0 and same_bytes(got, want, ar)
+
+
+def test_env_entry_points_refuse_a_misaligned_double_array(gpu):
+    """A double array 4 bytes past an 8-byte boundary: DRAGG_E_ARG from both entry points, and no byte is written."""
+    rng = np.random.default_rng(12)
+    for offs in ((4, 0, 0, 0), (0, 4, 0, 0), (12, 12, 0, 0)):
+        rc, ar, h0, got, want = _file_raw(gpu, 3, 2, 3, 2, offs, [1, 0], rng)
+        assert rc == -1 and np.array_equal(got, h0), ("file", offs)
+    for offs in ((0, 4, 0, 0), (0, 12, 0, 0)):
+        rc, ar, h0, got, want = _reset_raw(gpu, 3, 2, 3, 2, offs, [1, 1], rng)
+        assert rc == -1 and np.array_equal(got, h0), ("reset", offs)
+
+
 # ------------------------------------------------------------------ closed loops against the existing environment
 def _pair(community, T, P=12):
     from dragg_amd.rl import DeviceVectorEnv, VectorEnv

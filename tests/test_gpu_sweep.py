@@ -181,6 +181,57 @@ def test_replicate_raw_bits(gpu, Nb, G, H):
         assert torch.equal(df[g * Nb:(g + 1) * Nb], fc), g
 
 
+def _replicate_arena(L, Nb, G, H, src_off, dst_off):
+    from tests.arena import Arena
+    ar = Arena()
+    for side, n, off in (("src_", Nb, src_off), ("dst_", G * Nb, dst_off)):
+        ar.add(side + "vals", np.float64, (L.NVAL, n), off)
+        ar.add(side + "fc", np.float64, (n, L.NFC, H), off)
+    return ar
+
+
+def _replicate_at(L, lib, ar, rng, Nb, G, H, gpu):
+    """dragg_mpc_replicate on raw pointers into the arena -> (return code, the bytes before, after, expected by
+    the index rule: every replica g takes the base's columns / blocks, nothing else changes)."""
+    h0 = ar.random(rng)
+    want = h0.copy()
+    for g in range(G):
+        ar.view(want, "dst_vals")[:, g * Nb:(g + 1) * Nb] = ar.view(h0, "src_vals")
+        ar.view(want, "dst_fc")[g * Nb:(g + 1) * Nb] = ar.view(h0, "src_fc")
+    dev = ar.upload(h0, gpu)
+    dims = L.Dims(n_homes=G * Nb, horizon=H, sub_steps=6, dt=4, n_groups=G)
+    src = L.Hash(vals=ar.ptr(dev, "src_vals"), fc=ar.ptr(dev, "src_fc"))
+    dst = L.Hash(vals=ar.ptr(dev, "dst_vals"), fc=ar.ptr(dev, "dst_fc"))
+    rc = lib.dragg_mpc_replicate(ctypes.byref(dims), ctypes.byref(src), ctypes.byref(dst), L.stream_ptr())
+    torch.cuda.synchronize()
+    return rc, h0, dev.cpu().numpy(), want
+
+
+# bases 0 or 8 bytes past a 16-byte boundary: 16-byte units at Nb = 4 with both bases aligned, 8-byte units
+# otherwise (replicate moves doubles only: it has no 4-byte unit).  The last case: G = 5,000 replicas of 3 homes
+@pytest.mark.parametrize("Nb,G,H", [(1, 1, 3), (3, 1, 3), (4, 1, 3), (1, 3, 3), (3, 3, 3), (4, 3, 3), (3, 5000, 24)])
+def test_replicate_every_byte_at_offset_bases(gpu, Nb, G, H):
+    from dragg_amd import _lib as L
+    from tests.arena import same_bytes
+    lib = L.load()
+    rng = np.random.default_rng(100 * Nb + G)
+    for src_off, dst_off in ((0, 0), (8, 8), (0, 8), (8, 0)) if G < 5000 else ((8, 0),):
+        ar = _replicate_arena(L, Nb, G, H, src_off, dst_off)
+        rc, h0, got, want = _replicate_at(L, lib, ar, rng, Nb, G, H, gpu)
+        assert rc == 0 and same_bytes(got, want, ar), (src_off, dst_off)
+
+
+def test_replicate_refuses_a_misaligned_double_array(gpu):
+    """A base 4 bytes past an 8-byte boundary: DRAGG_E_ARG, and no byte is written."""
+    from dragg_amd import _lib as L
+    lib, Nb, G, H = L.load(), 3, 2, 3
+    rng = np.random.default_rng(4)
+    for src_off, dst_off in ((4, 0), (0, 4), (12, 12)):
+        ar = _replicate_arena(L, Nb, G, H, src_off, dst_off)
+        rc, h0, got, want = _replicate_at(L, lib, ar, rng, Nb, G, H, gpu)
+        assert rc == -1 and np.array_equal(got, h0), (src_off, dst_off)
+
+
 @pytest.mark.parametrize("Nb,G", [(7, 3), (1, 3), (64, 1)])
 def test_replicate_from_batch_states(gpu, community, Nb, G):
     from dragg_amd.mpc import MPCBatch

@@ -15,8 +15,9 @@ order every repetition (a b, b a, ...), with HIP events on the stream around the
 put back between actions outside the timed window.  Separately: the adopt kernel alone (events around
 --kernel-reps back-to-back `adopt_from` calls, the adopted copy rotated from call to call; bytes moved =
 2 x (NVAL 8 + NFC H 8 + the out members) per adopted home; at G = 1 the same bytes are copied every time and
-stay in the memory-side cache: a cache-warm rate) and, for the RL workload at --forecast-horizon > 1 steps,
-the clone of the first step's arrays.
+stay in the memory-side cache: a cache-warm rate), for the RL workload the replicate kernel alone (the same
+events around back-to-back `replicate_from` calls) and, at --forecast-horizon > 1 steps, the clone of the
+first step's arrays.
 Prints one JSON line and writes it to --out.  Needs a GPU (there is no fallback).
 
     python tools/commit_bench.py --out profiles/r10/commit/commit_line.json
@@ -156,8 +157,11 @@ def main():
             k_ms = kernel_time(lambda i: agg.batch.adopt_from(rb, chs[i % G:i % G + 1], hist=agg.hist[t]),
                                args.kernel_reps)
             nbytes = adopt_bytes(H, True) * agg.batch.N
+            # ... and the replicate kernel alone (the live state fanned out to the G replicas again)
+            rep_ms = kernel_time(lambda i: rb.replicate_from(agg.batch), args.kernel_reps)
             row = {"G": G, "today_ms": stats(ta), "held_ms": stats(tb),
                    "held_over_today": round(statistics.median(tb) / statistics.median(ta), 4),
+                   "replicate_kernel_ms": round(rep_ms, 4),
                    "adopt_kernel_ms": round(k_ms, 4), "adopt_bytes": nbytes,
                    "adopt_GBps": round(nbytes / (k_ms * 1e-3) / 1e9, 1), "state_bit_identical": True}
             if fh > 1:

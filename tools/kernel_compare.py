@@ -72,15 +72,27 @@ def main():
     a, b = sys.argv[1:3]
     with tempfile.TemporaryDirectory() as tmp:
         ka, kb = kernels(code_object(a, tmp, "a")), kernels(code_object(b, tmp, "b"))
+    # a kernel whose parameter types changed has a new mangled name: it is the same kernel if exactly one
+    # kernel of that function name is left over on either side
+    left_a, left_b = sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka))
+    resigned = {}
+    for k in left_a:
+        twins = [j for j in left_b if short(j) == short(k)]
+        if len(twins) == 1 and [short(j) for j in left_a].count(short(k)) == 1:
+            resigned[k] = twins[0]
+            kb[k] = kb.pop(twins[0])
     both = sorted(set(ka) & set(kb))
+    text = [k for k in both if ka[k]["text_sha"] != kb[k]["text_sha"]]
+    resources = [k for k in both if any(ka[k].get(f) != kb[k].get(f) for f in META.values())]
     res = {"how": "llvm-objdump -d of the gfx950 code object of both libraries (addresses and encodings stripped, "
                   "compared per kernel) and the resources in the code object's metadata",
            "kernels_first": len(ka), "kernels_second": len(kb),
            "only_in_first": sorted(short(k) for k in set(ka) - set(kb)),
            "new_in_second": {short(k): kb[k] for k in sorted(set(kb) - set(ka))},
-           "kernels_whose_instruction_text_changed": [short(k) for k in both if ka[k]["text_sha"] != kb[k]["text_sha"]],
-           "kernels_whose_resources_changed": [short(k) for k in both
-                                               if any(ka[k].get(f) != kb[k].get(f) for f in META.values())],
+           "kernels_whose_signature_changed": sorted(short(k) for k in resigned),
+           "kernels_whose_instruction_text_changed": [short(k) for k in text],
+           "kernels_whose_resources_changed": [short(k) for k in resources],
+           "changed_kernels_in_second": {short(k): kb[k] for k in sorted(set(text) | set(resources))},
            "common_kernels": {f"{short(k)}#{i}": ka[k] for i, k in enumerate(both)}}
     print(json.dumps(res, indent=1))
 
