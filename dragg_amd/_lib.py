@@ -107,6 +107,14 @@ class Plan(ctypes.Structure):
                 ("stats", c_dp)]
 
 
+class Paths(ctypes.Structure):
+    """dragg_mpc_paths: the K-step rollouts of C candidates per episode and the outputs of dragg_mpc_select_paths
+    (choice [E], score [C * E] or NULL)."""
+    _fields_ = [("steps", ctypes.c_int32), ("num_timesteps", ctypes.c_int32), ("prev_timesteps", ctypes.c_int32),
+                ("fresh_load", ctypes.c_double), ("sums", c_dp), ("ran", c_dp), ("tracked", c_dp), ("target", c_dp),
+                ("weights", c_dp), ("prices", c_dp), ("n_rp", ctypes.c_int32), ("choice", c_dp), ("score", c_dp)]
+
+
 PLAN_WAYS = 16                 # DRAGG_PLAN_WAYS: the partial sums of a plan entry (part of its summation order)
 # the forecast keys a plan curve can hold (dragg_fc_key, bit k of dragg_mpc_plan.fc_keys) and the vals rows a plan
 # statistic can hold (dragg_val, bit r of val_rows), by their short names
@@ -195,7 +203,7 @@ EXPORTS = ["dragg_mpc_abi_version", "dragg_mpc_strerror", "dragg_mpc_lds_bytes",
            "dragg_mpc_side_workspace_bytes", "dragg_mpc_side_grid", "dragg_mpc_source_hash",
            "dragg_mpc_replicate", "dragg_mpc_aggregate_groups", "dragg_mpc_step_episodes",
            "dragg_mpc_season_noise_episodes", "dragg_mpc_adopt", "dragg_mpc_select_groups", "dragg_mpc_env_file",
-           "dragg_mpc_env_reset", "dragg_mpc_plan_groups"]
+           "dragg_mpc_env_reset", "dragg_mpc_plan_groups", "dragg_mpc_select_paths"]
 
 _LIB = None
 
@@ -268,6 +276,7 @@ def load(path=LIB_PATH):
     lib.dragg_mpc_env_file.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Env), ctypes.POINTER(Out), c_dp]
     lib.dragg_mpc_env_reset.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Env), c_dp, ctypes.POINTER(Hash), c_dp]
     lib.dragg_mpc_plan_groups.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Hash), ctypes.POINTER(Plan), c_dp]
+    lib.dragg_mpc_select_paths.argtypes = [ctypes.POINTER(Dims), ctypes.c_int32, ctypes.POINTER(Paths), c_dp]
     if lib.dragg_mpc_abi_version() != ABI_VERSION:
         raise DraggError("ABI version mismatch between dragg_amd and libdragg_mi355x.so")
     if not os.environ.get("DRAGG_LIB"):

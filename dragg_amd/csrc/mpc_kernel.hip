@@ -5174,18 +5174,15 @@ struct EnvArgs {
     double *max_load, *min_load, *tracked, *obs;
 };
 
-// rl.setpoint_update (Aggregator.gen_setpoint's rule) for one episode, by one lane, bit for bit: the tracked
-// loads start over (`fresh`: timestep < 2) or the oldest makes room for `load`; their average is numpy's
-// (np.average of P doubles = pairwise_sum / P: below 8 elements a left-to-right sum from 0.0; from 8 to 128
-// eight accumulators over the whole blocks of 8, combined as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)),
-// then the rest left to right); then the max / min rule.  Each block of 8 is loaded before it is stored (the
-// shift reads element i + 1 for element i) and so that the loads of a block are in flight together.
-DEV void env_setpoint(const EnvArgs& a, int g, int timestep, double load, double forecast, double cost, bool fresh) {
+// The average of the P tracked loads next(0) .. next(P - 1) as numpy takes it (np.average of P doubles =
+// pairwise_sum / P: below 8 elements a left-to-right sum from 0.0; from 8 to 128 eight accumulators over the
+// whole blocks of 8, combined as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the rest left to right),
+// each load handed to keep(i, v) on the way: the environment stores its shifted window there,
+// dragg_mpc_select_paths keeps nothing.  Each block of 8 is loaded before it is kept (the environment's shift
+// reads element i + 1 for element i) and so that the loads of a block are in flight together.
+template <class Next, class Keep>
+DEV double tracked_average(int P, Next next, Keep keep) {
 #pragma clang fp contract(off)   // bit-identical to numpy's sum and division
-    const int P = a.P;
-    double* tr = a.tracked + (size_t)g * P;
-    double mx = fresh ? -__builtin_inf() : a.max_load[g], mn = fresh ? __builtin_inf() : a.min_load[g];
-    auto next = [&](int i) { return fresh ? a.fresh_load : i < P - 1 ? tr[i + 1] : load; };
     double res = 0.0;
     int i = 0;
     if (P >= 8) {
@@ -5197,7 +5194,7 @@ DEV void env_setpoint(const EnvArgs& a, int g, int timestep, double load, double
             for (int j = 0; j < 8; ++j) v[j] = next(i + j);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                tr[i + j] = v[j];
+                keep(i + j, v[j]);
                 r[j] = i == 0 ? v[j] : r[j] + v[j];
             }
         }
@@ -5205,10 +5202,21 @@ DEV void env_setpoint(const EnvArgs& a, int g, int timestep, double load, double
     }
     for (; i < P; ++i) {
         const double v = next(i);
-        tr[i] = v;
+        keep(i, v);
         res += v;
     }
-    const double avg = res / (double)P;
+    return res / (double)P;
+}
+
+// rl.setpoint_update (Aggregator.gen_setpoint's rule) for one episode, by one lane, bit for bit: the tracked
+// loads start over (`fresh`: timestep < 2) or the oldest makes room for `load`; their average (above); then the
+// max / min rule.
+DEV void env_setpoint(const EnvArgs& a, int g, int timestep, double load, double forecast, double cost, bool fresh) {
+    const int P = a.P;
+    double* tr = a.tracked + (size_t)g * P;
+    double mx = fresh ? -__builtin_inf() : a.max_load[g], mn = fresh ? __builtin_inf() : a.min_load[g];
+    const double avg = tracked_average(P, [&](int i) { return fresh ? a.fresh_load : i < P - 1 ? tr[i + 1] : load; },
+                                       [&](int i, double v) { tr[i] = v; });
     const bool day = timestep % 24 == 0;
     if (load > mx || day) mx = load;
     if (load < mn || day) mn = load;
@@ -5257,6 +5265,85 @@ __global__ __launch_bounds__(REP_NT) void env_reset_kernel(EnvArgs a) {
         *seg_at<T>(s.dst, r * s.dst_stride + g * s.group_bytes, i) = v;
     });
     if (blockIdx.x == 0 && threadIdx.x == 0) env_setpoint(a, g, 0, a.start_load, a.start_load, 0.0, true);
+}
+
+// dragg_mpc_select_paths: the choice over K-step rollouts.  Block e (one wave) owns episode e, a lane one of its
+// candidates, 64 at a time in ascending c: the lane walks its candidate's K loads, rebuilding for step j the
+// window gen_setpoint would hold after j plays -- element i of it is tracked[i + n] while that exists, then the
+// rollout's own loads, with n the loads shifted in so far; a rollout from clock 0 starts over at step 1, so its
+// window is fresh_load and its load 0 never enters -- and averaging it with env_setpoint's own arithmetic
+// (tracked_average).  Nothing is kept: the window is a function of `tracked` and the loads.  The per-episode
+// values (ran, target, the tracked loads, the weights) are uniform over the block and come by scalar loads.
+// The 64 scores and |prices| then go through LDS and lane 0 scans them in ascending c with select_groups_kernel's
+// comparison, so the tie rule is the sequential one whatever C is.
+constexpr int PATHS_NT = WAVE;
+struct PathsArgs {
+    int E, C, K, T, P, n_rp;
+    int empty;                          // n_homes == 0: no episode has a step to choose
+    double fresh_load;
+    const double *sums, *tracked, *target, *weights, *prices;
+    const int32_t* ran;
+    int32_t* choice;
+    double* score;
+};
+__global__ __launch_bounds__(PATHS_NT) void select_paths_kernel(PathsArgs a) {
+#pragma clang fp contract(off)   // the score is a product, then a sum: the host's doubles
+    __shared__ double s_score[PATHS_NT], s_price[PATHS_NT];
+    __shared__ int s_valid[PATHS_NT];
+    const int e = (int)blockIdx.x, lane = (int)threadIdx.x;
+    const int t = __builtin_amdgcn_readfirstlane(a.ran[e]);
+    const int k = a.empty || t < 0 || t >= a.T ? 0 : min(a.K, a.T - t);
+    const size_t step = (size_t)a.C * a.E * 3;              // doubles between two rollout steps of a group
+    const double* tr = a.tracked + (size_t)e * a.P;
+    const double s0 = a.target[e];
+    const int j0 = t == 0 ? 1 : 0;
+    const double nan = __builtin_nan("");
+    int best = -1;
+    double bd = 0.0, bp = 0.0;
+    for (int c0 = 0; c0 < a.C; c0 += PATHS_NT) {
+        const int c = c0 + lane;
+        double acc = nan, p = 0.0;
+        bool valid = false;
+        if (c < a.C) {
+            const size_t g = (size_t)c * a.E + e;
+            const double* l = a.sums + g * 3;
+            if (k > 0) {
+                valid = true;
+                acc = 0.0;
+                for (int j = 0; j < k; ++j) {
+                    const double load = l[j * step];
+                    if (load != load) { valid = false; break; }
+                    double s = s0;
+                    if (j > 0) {
+                        const int n = j - j0;
+                        s = tracked_average(a.P, [&](int i) {
+                            const int q = i + n;
+                            return q >= a.P ? l[(size_t)(j0 + q - a.P) * step] : j0 ? a.fresh_load : tr[q];
+                        }, [](int, double) {});
+                    }
+                    const double d = a.weights[j] * fabs(load - s);
+                    acc = acc + d;
+                }
+                if (!valid) acc = nan;
+                p = fabs(a.prices[g * (size_t)a.n_rp]);
+            }
+            if (a.score) a.score[g] = acc;
+        }
+        s_score[lane] = acc;
+        s_price[lane] = p;
+        s_valid[lane] = valid;
+        __syncthreads();
+        if (lane == 0) {
+            const int n = min(PATHS_NT, a.C - c0);
+            for (int i = 0; i < n; ++i) {
+                if (!s_valid[i]) continue;
+                const double d = s_score[i], q = s_price[i];
+                if (best < 0 || d < bd || (d == bd && q < bp)) { best = c0 + i; bd = d; bp = q; }
+            }
+        }
+        __syncthreads();
+    }
+    if (lane == 0) a.choice[e] = best;
 }
 
 // Plan observations (dragg_mpc_plan_groups): per group the time-aligned horizon curves of the chosen forecast
@@ -6054,6 +6141,34 @@ int dragg_mpc_env_reset(const dragg_mpc_dims* dims, const dragg_mpc_env* env, co
     if (env->agg_hist) ok = ok && env_seg(a, nullptr, env->agg_hist, 3 * 8, T, 8, 0);
     if (!ok) return DRAGG_E_ARG;
     return seg_launch(env_reset_kernel, a, G, stream);
+}
+
+int dragg_mpc_select_paths(const dragg_mpc_dims* dst_dims, int32_t copies, const dragg_mpc_paths* p, void* stream) {
+    if (!dst_dims || dst_dims->n_homes < 0 || copies < 1 || !p) return DRAGG_E_ARG;
+    if (p->steps < 1 || p->num_timesteps < 1 || p->prev_timesteps < 1 || p->prev_timesteps > DRAGG_ENV_PREV_MAX ||
+        p->n_rp < 1) return DRAGG_E_ARG;
+    if (!p->sums || !p->ran || !p->tracked || !p->target || !p->weights || !p->prices || !p->choice) return DRAGG_E_ARG;
+    const int E = group_count(dst_dims);
+    if (E < 0) return DRAGG_E_ARG;
+    PathsArgs a{};
+    a.E = E;
+    a.C = copies;
+    a.K = p->steps;
+    a.T = p->num_timesteps;
+    a.P = p->prev_timesteps;
+    a.n_rp = p->n_rp;
+    a.empty = dst_dims->n_homes == 0;
+    a.fresh_load = p->fresh_load;
+    a.sums = p->sums;
+    a.tracked = p->tracked;
+    a.target = p->target;
+    a.weights = p->weights;
+    a.prices = p->prices;
+    a.ran = p->ran;
+    a.choice = p->choice;
+    a.score = p->score;
+    hipLaunchKernelGGL(select_paths_kernel, dim3(E), dim3(PATHS_NT), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
 }
 
 int dragg_mpc_plan_groups(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, const dragg_mpc_plan* plan,

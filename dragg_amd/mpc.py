@@ -478,14 +478,57 @@ class MPCBatch:
             self._keep = (sums, target, prices)
             return choice
 
-    def aggregate_groups(self, stream=None):
+    def select_paths(self, sums, ran, tracked, target, weights, prices, num_timesteps, fresh_load, score=None,
+                     stream=None):
+        """The choice for `adopt_from` over K-step rollouts, made on the device (dragg_mpc_select_paths): `sums`
+        [K][C * E][3] (`aggregate_groups` of the copies' batch after each rollout step), `ran` int32 [E] (the
+        clocks step 0 ran with; outside [0, num_timesteps): no step), `tracked` [E][P] and `target` [E] (the
+        setpoint rule's tracked loads and setpoint now), `weights` [K], `prices` [C * E][n] -- contiguous device
+        tensors, read as they are.  Per episode the candidate of least weighted distance between its loads and
+        the setpoints the rule would file if it were played; ties to the smaller |price|, then the smaller copy;
+        -1 where none is valid.  `score`: a contiguous device float64 tensor of C * E entries for the scores
+        (copy-major), or None.  -> device int32 [E].  No synchronisation."""
+        E = max(self.groups, 1)
+        dev = self.device
+        for name, x, dt in (("sums", sums, torch.float64), ("ran", ran, torch.int32), ("tracked", tracked, torch.float64),
+                            ("target", target, torch.float64), ("weights", weights, torch.float64),
+                            ("prices", prices, torch.float64), ("score", score, torch.float64)):
+            if x is None and name == "score":
+                continue
+            if not torch.is_tensor(x) or x.device != dev or x.dtype != dt or not x.is_contiguous():
+                raise ValueError(f"select_paths: {name} must be a contiguous device tensor of {dt}")
+        if sums.dim() != 3 or sums.shape[2] != 3 or sums.shape[1] < E or sums.shape[1] % E or sums.shape[0] < 1:
+            raise ValueError(f"select_paths takes sums [K][C * {E}][3], not {list(sums.shape)}")
+        K, CE = int(sums.shape[0]), int(sums.shape[1])
+        if tracked.dim() != 2 or tracked.shape[0] != E or ran.numel() != E or target.numel() != E \
+                or weights.numel() != K or prices.dim() != 2 or prices.shape[0] != CE \
+                or (score is not None and score.numel() != CE):
+            raise ValueError(f"select_paths takes ran [{E}], tracked [{E}][P], target [{E}], weights [{K}], prices "
+                             f"[{CE}][n] and score [{CE}]")
+        with torch.cuda.device(dev):
+            choice = torch.empty(E, dtype=torch.int32, device=dev)
+            p = L.Paths(steps=K, num_timesteps=int(num_timesteps), prev_timesteps=int(tracked.shape[1]),
+                        fresh_load=float(fresh_load), sums=L.ptr(sums), ran=L.ptr(ran), tracked=L.ptr(tracked),
+                        target=L.ptr(target), weights=L.ptr(weights), prices=L.ptr(prices),
+                        n_rp=int(prices.shape[1]), choice=L.ptr(choice), score=L.ptr(score))
+            L.check(self.lib.dragg_mpc_select_paths(self.dims, CE // E, p, L.stream_ptr(stream, dev)))
+            self._keep = (sums, ran, tracked, target, weights, prices, score)
+            return choice
+
+    def aggregate_groups(self, stream=None, out=None):
         """collect_data's sums of every group -> device tensor [G][3]; row g is bit-identical to
-        aggregate() of a batch holding replica g's homes (dragg_mpc_aggregate_groups)."""
+        aggregate() of a batch holding replica g's homes (dragg_mpc_aggregate_groups).  `out`: a contiguous
+        device float64 tensor of G * 3 entries to write instead of the batch's own rows."""
         with torch.cuda.device(self.device):
-            if getattr(self, "agg_groups", None) is None:
-                self.agg_groups = torch.zeros((self.groups, 3), dtype=torch.float64, device=self.device)
-            self._call(self.lib.dragg_mpc_aggregate_groups, self._hash(), L.ptr(self.agg_groups), stream=stream)
-            return self.agg_groups
+            if out is None:
+                if getattr(self, "agg_groups", None) is None:
+                    self.agg_groups = torch.zeros((self.groups, 3), dtype=torch.float64, device=self.device)
+                out = self.agg_groups
+            elif not torch.is_tensor(out) or out.device != self.device or out.dtype != torch.float64 \
+                    or out.numel() != self.groups * 3 or not out.is_contiguous():
+                raise ValueError(f"aggregate_groups: out must be a contiguous device float64 tensor [{self.groups}][3]")
+            self._call(self.lib.dragg_mpc_aggregate_groups, self._hash(), L.ptr(out), stream=stream)
+            return out
 
     # ------------------------------------------------------------------ plan observations
     def plan_groups(self, keys, rows=(), out=None, stream=None, src=None):

@@ -168,6 +168,16 @@ class SetpointAgent:
         return a / torch.full_like(a, self.scale)
 
 
+def _path_weights(K, weights):
+    """The K step weights of a lookahead score as host doubles (None: ones)."""
+    if weights is None:
+        return np.ones(K)
+    w = np.asarray(weights.cpu() if hasattr(weights, "cpu") else weights, dtype=float).reshape(-1)
+    if len(w) != K:
+        raise ValueError(f"a lookahead of {K} steps takes {K} weights, not {len(w)}")
+    return w
+
+
 class VectorEnv:
     """E episodes of one community as a vector environment for reward-price policies, on a
     `dragg_amd.vector.VectorAggregator`.
@@ -196,6 +206,7 @@ class VectorEnv:
         self.agg_cost = np.zeros(self.E)
         self.agg_setpoint = np.zeros(self.E)
         self._sp = [None] * self.E
+        self.scores = None
 
     def _host_mask(self, mask):
         return np.asarray(episode_mask(mask.cpu() if hasattr(mask, "cpu") else mask, self.E))
@@ -249,16 +260,37 @@ class VectorEnv:
             self._setpoint(e)
         return self.observations(), self.done()
 
-    def step_swept(self, candidates):
+    def step_swept(self, candidates, lookahead=1, weights=None):
         """`step` with the price chosen from C candidates per episode (`candidates` [E][C] or [E][C][n], $/kWh)
         instead of guessed: every candidate of every active episode is solved one step ahead in one batch
         (`VectorAggregator.sweep`), the one whose load lies closest to the episode's setpoint is chosen on
         the device (`select`: ties to the smaller |price|, then the smaller index) and its solved step
         adopted (`commit`) -- no second solve.  -> (observations, done [E]); `self.choice` holds the chosen
-        indices ([E] numpy, -1: the episode took no step)."""
+        indices ([E] numpy, -1: the episode took no step).
+
+        lookahead = K > 1: every candidate is rolled K steps ahead (`sweep(steps=K)`) and scored over its load
+        path, step j weighted by `weights[j]` (default: ones) against the setpoint this environment would hold
+        by then had the candidate been played (`vector.select_paths_reference`, on the host here); the chosen
+        candidate's FIRST step is adopted.  `self.scores` holds the scores ([E][C] numpy, NaN: none)."""
         on = ~self.parked & ~self.done()
-        sums = self.va.sweep(candidates)
-        choice = self.va.select(sums, self.agg_setpoint, candidates)
+        K = int(lookahead)
+        if K > 1:
+            import torch
+            from .vector import select_paths_reference
+            paths = self.va.sweep(candidates, steps=K).cpu().numpy()                  # [E][C][K][3]
+            C = paths.shape[1]
+            P = int(self.prev_timesteps)
+            fresh = [0.5 * self.max_poss_load] * P
+            ch, score = select_paths_reference(
+                paths.transpose(2, 1, 0, 3).reshape(K, C * self.E, 3), np.where(on, self.timestep, -1),
+                [fresh if sp is None else sp[0] for sp in self._sp], self.agg_setpoint, _path_weights(K, weights),
+                np.asarray(candidates.cpu() if hasattr(candidates, "cpu") else candidates, dtype=float)
+                .reshape(self.E, C, -1).transpose(1, 0, 2), self.T, self.max_poss_load)
+            self.scores = score.reshape(C, self.E).T.copy()
+            choice = torch.as_tensor(ch, dtype=torch.int32, device=self.va.device)
+        else:
+            sums = self.va.sweep(candidates)
+            choice = self.va.select(sums, self.agg_setpoint, candidates)
         agg = self.va.commit(choice).cpu().numpy()
         adopted = self.va.adopted.cpu().numpy()
         self.choice = np.where(adopted, choice.cpu().numpy(), -1)
@@ -302,7 +334,8 @@ class DeviceVectorEnv:
         self.max_poss_load = (sum(I.max_load(h) for h in va.homes) if max_poss_load is None else max_poss_load)
         self.n_homes = va.Nb if n_homes is None else int(n_homes)
         self.state = va.env_state(self.prev_timesteps, self.max_poss_load, 3 * self.n_homes)
-        self.choice = None
+        self.choice = self.scores = None
+        self._w = {}
         _, _, ki, ri = L.plan_select(plan_keys, plan_rows)
         self.plan_key_names, self.plan_row_names = [L.PLAN_KEYS[k] for k in ki], [L.PLAN_ROWS[r] for r in ri]
         self._plan = None
@@ -344,12 +377,36 @@ class DeviceVectorEnv:
         self._observe_plan()
         return self.observations(), self.done()
 
-    def step_swept(self, candidates):
-        """-> (observations, done [E]), as `VectorEnv.step_swept`; the setpoints go to `select` from the device."""
+    def _weights(self, K, weights):
+        """The K step weights as a device tensor: a device tensor as it is, a host list (None: ones) uploaded
+        once and cached per (K, device)."""
+        import torch
+        dev = self.va.device
+        if torch.is_tensor(weights) and weights.device == dev:
+            return weights
+        vals = None if weights is None else tuple(_path_weights(K, weights).tolist())
+        hit = self._w.get((K, dev))
+        if hit is None or hit[0] != vals:
+            hit = self._w[(K, dev)] = (vals, torch.ones(K, dtype=torch.float64, device=dev) if vals is None
+                                       else torch.tensor(vals, dtype=torch.float64).to(dev))
+        return hit[1]
+
+    def step_swept(self, candidates, lookahead=1, weights=None):
+        """-> (observations, done [E]), as `VectorEnv.step_swept`; the setpoints go to `select` from the device.
+        lookahead = K > 1: the K-step rollouts are scored and the choice made by one kernel
+        (`VectorAggregator.select_paths`) from the tracked loads, setpoints and clocks where they live;
+        `self.scores` is a device view [E][C] (overwritten by the next call), bit for bit `VectorEnv`'s."""
         import torch
         va = self.va
-        sums = va.sweep(candidates)
-        choice = va.select(sums, self.state.obs[3], candidates)
+        K = int(lookahead)
+        if K > 1:
+            paths = va.sweep(candidates, steps=K)
+            choice = va.select_paths(paths, self.state.tracked, self.state.obs[3], candidates,
+                                     self._weights(K, weights), self.max_poss_load)
+            self.scores = va.path_scores
+        else:
+            sums = va.sweep(candidates)
+            choice = va.select(sums, self.state.obs[3], candidates)
         va.commit_env(self.state, choice)
         self.choice = torch.where(va.adopted, choice, torch.full_like(choice, -1))
         self._observe_plan()
@@ -364,12 +421,17 @@ class SweepAgent:
     smaller |price|.  `history` keeps every step's candidates, their responses (the first step's
     aggregate load per candidate) and the choice.  commit=True (`rl.parameters.commit`): the sweep is held
     and `act` returns a `Candidate`, so that `run_rl_agg` plays the chosen candidate by adopting its solved
-    step instead of solving it again (`Aggregator.rl_commit`; the results are the same bit for bit)."""
+    step instead of solving it again (`Aggregator.rl_commit`; the results are the same bit for bit).
+    lookahead = K > 1 (`rl.parameters.lookahead`): every candidate is rolled K steps ahead and scored over its
+    load path, step j weighted by discount**j (`rl.parameters.discount`) against the setpoint `gen_setpoint`
+    would hold by then had it been played -- the rule of the vector environments' `step_swept(lookahead=K,
+    weights=agent.weights())`; `history["score"]` keeps the scores.  The first step is what is played."""
 
     name = "sweep"
 
-    def __init__(self, config, n_candidates=8, commit=False):
+    def __init__(self, config, n_candidates=8, commit=False, lookahead=1, discount=1.0):
         self.commit = bool(commit)
+        self.lookahead, self.discount = max(1, int(lookahead)), float(discount)
         self.index = None
         util = config["rl"]["utility"]
         lo, hi = util["action_space"]
@@ -381,13 +443,41 @@ class SweepAgent:
     def candidates(self):
         return np.clip(np.linspace(self.lo, self.hi, self.n), self.lo, self.hi)
 
+    def weights(self):
+        """The step weights of the lookahead score, discount**j for j < lookahead (what a caller hands
+        `step_swept(candidates, lookahead=agent.lookahead, weights=agent.weights())`)."""
+        return [self.discount ** j for j in range(self.lookahead)]
+
+    def _train_ahead(self, env, prices):
+        """`train`'s choice with lookahead > 1: the candidates rolled `lookahead` steps ahead
+        (`rl_sweep(prices, steps=K)`) and scored by the vector environments' rule (`select_paths_reference`, one
+        episode) on the runner's own `gen_setpoint` state.  -> (index, first-step loads), or None when the run has
+        no step left (the caller's tie rule decides)."""
+        from .vector import select_paths_reference
+        resp = np.asarray(env.rl_sweep(prices, steps=self.lookahead, hold=self.commit), dtype=float)   # [C][k][3]
+        k = resp.shape[1]
+        if not k:
+            return None
+        choice, score = select_paths_reference(
+            resp.transpose(1, 0, 2), [int(env.timestep)], [list(env.tracked_loads)], [float(env.agg_setpoint)],
+            self.weights()[:k], np.asarray(prices).reshape(len(prices), 1), env.num_timesteps, env.max_poss_load)
+        self.history.setdefault("score", []).append(score.tolist())
+        return int(choice[0]), resp[:, 0, 0]
+
     def train(self, env):
         acts = self.candidates()
         prices = [float(a) / self.scale for a in acts]
+        ahead = self._train_ahead(env, prices) if self.lookahead > 1 else None
+        if ahead is not None and ahead[0] >= 0:
+            best, load = ahead
+            return self._chosen(acts, load, best)
         resp = np.asarray(env.rl_sweep(prices, hold=True) if self.commit else env.rl_sweep(prices), dtype=float)
         load = resp[:, 0, 0] if resp.shape[1] else np.zeros(len(acts))   # (no step left in the run: all tie)
         sp = float(env.agg_setpoint)
         best = min(range(len(acts)), key=lambda i: (abs(load[i] - sp), abs(acts[i])))
+        return self._chosen(acts, load, best)
+
+    def _chosen(self, acts, load, best):
         a = float(np.clip(acts[best], self.lo, self.hi))
         self.index = best
         self.history["candidates"].append(acts.tolist())
@@ -424,9 +514,12 @@ def agent_policy(aggregator):
     `rl.parameters.learning_rate` (README.md:58-63) is a learning agent's step size, not a controller
     gain: it is left to an agent wrapped by `policy_from_agent`.  `rl.parameters.policy = "sweep"`
     selects `SweepAgent` instead, with `rl.parameters.candidates` (default 8) candidate prices;
-    `rl.parameters.commit = true` makes it play the chosen candidate by adopting its solved step."""
+    `rl.parameters.commit = true` makes it play the chosen candidate by adopting its solved step;
+    `rl.parameters.lookahead` (default 1: one step ahead) and `rl.parameters.discount` (default 1.0) make it
+    score the candidates over that many steps."""
     p = aggregator.config.get("rl", {}).get("parameters", {}) or {}
     if p.get("policy") == "sweep":
         return SweepAgent(aggregator.config, n_candidates=int(p.get("candidates", 8)),
-                          commit=bool(p.get("commit", False))).act
+                          commit=bool(p.get("commit", False)), lookahead=int(p.get("lookahead", 1)),
+                          discount=float(p.get("discount", 1.0))).act
     return SetpointAgent(aggregator.config, kp=float(p.get("kp", 1.0)), ki=float(p.get("ki", 0.1))).act

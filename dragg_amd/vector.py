@@ -19,6 +19,11 @@ environment's setpoint state and observations (dragg_mpc_env_file), and one kern
 episodes over by writing their columns alone (dragg_mpc_env_reset).  `env_file_reference` and
 `env_reset_reference` restate the two kernels on numpy arrays for the tests.
 
+`sweep(prices, steps=K)` rolls every candidate of every episode K steps ahead as one grouped batch and
+`select_paths` scores the K-step load paths against the setpoints the environment's rule would file along them
+(dragg_mpc_select_paths; `select_paths_reference` restates it), so that a policy sees a price's rebound before it
+plays the first step.
+
 `plan` reduces the plans the episodes' last solves left in the hash arrays to per-episode horizon curves
 (dragg_mpc_plan_groups; `plan_groups_reference` restates it, summation order included).
 
@@ -129,6 +134,54 @@ def env_reset_reference(env, mask, vals, fc):
         env["obs"][:, g] = (load, load, 0.0, avg, 0)
 
 
+def select_paths_reference(sums, ran, tracked, target, weights, prices, num_timesteps, max_poss_load, setpoints=None):
+    """dragg_mpc_select_paths restated on numpy arrays (the spec its tests share, the scoring of the host
+    `rl.VectorEnv` and of `SweepAgent.train`, and what a stand-in batch serves `select_paths` with -- not a
+    solver fallback).  `sums` [K][C * E][3] (copy-major groups c * E + e), `ran` [E], `tracked` [E][P], `target`
+    [E], `weights` [K], `prices` [C * E][n] -> (choice int32 [E], score float64 [C * E]).  Candidate c of episode
+    e is scored over its k = min(K, T - ran[e]) steps against the setpoints `rl.setpoint_update` itself returns
+    when the candidate's loads are played on a copy of the episode's tracked loads; `setpoints` (a dict, for the
+    tests) receives the list [s_0 .. s_(k-1)] per (e, c) that was scored to its end.  Nothing given is written."""
+    from .rl import setpoint_update
+    sums = np.asarray(sums, dtype=np.float64)
+    K, CE = sums.shape[0], sums.shape[1]
+    E = len(ran)
+    C, T = CE // E, int(num_timesteps)
+    tracked = np.asarray(tracked, dtype=np.float64).reshape(E, -1)
+    P = tracked.shape[1]
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    prices = np.asarray(prices, dtype=np.float64).reshape(CE, -1)
+    choice, score = np.full(E, -1, dtype=np.int32), np.full(CE, np.nan)
+    for e in range(E):
+        t = int(ran[e])
+        k = min(K, T - t) if 0 <= t < T else 0
+        best, bd, bp = -1, 0.0, 0.0
+        for c in range(C if k > 0 else 0):
+            g = c * E + e
+            state = (tracked[e].tolist(), -float("inf"), float("inf"))
+            s, acc, sps = np.float64(target[e]), np.float64(0.0), []
+            for j in range(k):
+                load = sums[j, g, 0]
+                if load != load:
+                    acc = None
+                    break
+                if j > 0:
+                    *state, s = setpoint_update(state, t + j, float(sums[j - 1, g, 0]), max_poss_load, P)
+                sps.append(float(s))
+                d = w[j] * np.abs(load - s)
+                acc = acc + d
+            if acc is None:
+                continue
+            if setpoints is not None:
+                setpoints[(e, c)] = sps
+            score[g] = acc
+            p = np.abs(prices[g, 0])
+            if best < 0 or acc < bd or (acc == bd and p < bp):
+                best, bd, bp = c, acc, p
+        choice[e] = best
+    return choice, score
+
+
 def plan_groups_reference(vals, fc, G, keys, rows=()):
     """dragg_mpc_plan_groups restated on numpy arrays with explicit loops in the contract's order (the spec its
     CPU and GPU tests share, and what a stand-in batch serves `plan_groups` with -- not a solver fallback).
@@ -179,6 +232,28 @@ def plan_groups_reference(vals, fc, G, keys, rows=()):
     return curve, count, stats
 
 
+class HeldReplicas:
+    """The first step of a K-step sweep, kept while its replica batch moves on: the arrays `MPCBatch.adopt_from`
+    reads (`aggregator.HeldStep`'s), but allocated once and refilled with `copy_` -- an environment step never
+    calls the allocator for them.  The history row is the replica batch's own: only step 0 writes it."""
+    KEYS = ("vals", "fc_store", "status", "iters", "obj", "relax_obj", "int_path")
+
+    def __init__(self, rb):
+        self.N, self.H, self.groups = rb.N, rb.H, getattr(rb, "groups", 1)
+        for k in self.KEYS:
+            v = getattr(rb, k, None)
+            setattr(self, k, torch.empty_like(v) if v is not None else None)
+        # (fc is a view of fc_store where a batch has one: MPCBatch)
+        self.fc = self.fc_store.permute(1, 2, 0) if self.fc_store is not None else torch.empty_like(rb.fc)
+
+    def fill(self, rb):
+        for k in self.KEYS if self.fc_store is not None else self.KEYS + ("fc",):
+            v = getattr(self, k)
+            if v is not None:
+                v.copy_(getattr(rb, k))
+        self.hist_row = getattr(rb, "hist_row", None)
+
+
 class VectorAggregator:
     def __init__(self, homes, oat, ghi, tou, episodes, seeds, start_indices, num_timesteps, int_mode="round",
                  keep_history=True, device=None, batch_cls=MPCBatch, rank=0, world=1, **batch_kw):
@@ -211,6 +286,9 @@ class VectorAggregator:
         self.agg_hist = torch.zeros((T, E, 3), dtype=torch.float64, device=dev)
         self._batch_args = (batch_cls, dict(int_mode=int_mode, device=dev, **batch_kw))
         self._sweep_batches = {}     # C -> the C * E-group batch of sweep()
+        # K-step sweeps: (C, K) -> the sums [K][C * E][3], C -> the held first step, C -> the scores [C * E]
+        self._path_sums, self._held, self._path_score = {}, {}, {}
+        self.sweep_steps = self.path_scores = None
         # a held sweep (sweep -> commit) and the moves of the live state that void it (step, reset, commit)
         self._hold = None
         self._gen = 0
@@ -346,11 +424,11 @@ class VectorAggregator:
         return agg
 
     # ------------------------------------------------------------------ sweep, select, commit
-    # C candidate prices per episode, one step ahead: a batch of C * E groups holds C copies of the live
+    # C candidate prices per episode, one step ahead or K: a batch of C * E groups holds C copies of the live
     # E-group batch, copy-major (group c * E + e = episode e under its candidate c), filled by
-    # dragg_mpc_replicate and stepped once with the episodes' keys and clocks tiled C times.  `commit` then
-    # adopts, per episode, the chosen copy's solved step (dragg_mpc_adopt) instead of solving it again; the
-    # choice can be made on the device (`select`), so none of this synchronises with the host.
+    # dragg_mpc_replicate and stepped (K times) with the episodes' keys and clocks tiled C times.  `commit` then
+    # adopts, per episode, the chosen copy's solved first step (dragg_mpc_adopt) instead of solving it again;
+    # the choice can be made on the device (`select`, `select_paths`), so none of this synchronises with the host.
     def _sweep_batch(self, C):
         rb = self._sweep_batches.get(C)
         if rb is None:
@@ -364,12 +442,26 @@ class VectorAggregator:
             rb.dims.n_env = self.batch.dims.n_env
         return rb
 
-    def sweep(self, prices, hold=True):
+    def sweep(self, prices, steps=1, hold=True):
         """Every active episode's next step under each of its C candidate prices (`prices` [E][C], or
         [E][C][n] with n == 1 or n >= H), nothing committed -> device tensor [E][C][3], row (e, c)
         bit-identical to what `step` returns for episode e under prices[e][c] (an idle episode's rows: its
-        state's sums).  One step ahead only.  The live batch is only read.  hold=True (default) keeps the
-        solved replicas for `commit`."""
+        state's sums).  The live batch is only read.  hold=True (default) keeps the solved replicas for
+        `commit`.
+
+        steps = K > 1: every candidate is rolled K steps ahead under its price row -> [E][C][K][3].  Step 0 is
+        the step above; step j steps the same C * E replicas on with the same seeds and starts at the clocks
+        + j.  A replica whose episode has no step j left (clock + j >= num_timesteps, or idle at step 0) is idle
+        from then on: `self.sweep_steps` (device int32 [E]) holds the steps k_e each episode's replicas took,
+        row (e, c, j), j < k_e, is bit-identical to the sums after j + 1 `step`s under prices[e][c], and the
+        rows j >= k_e repeat row k_e - 1.  hold=True then keeps a copy of the replicas' FIRST step for `commit`
+        (the replicas themselves move on), in buffers allocated once per C.  Extra device memory for K > 1:
+        that copy -- the replica batch's hash arrays and per-home outputs over again, C * E * Nb * (NVAL + NFC *
+        H + 5) doubles' worth, about C times the live batch -- and K * C * E * 3 doubles of sums per (C, K).  No
+        host synchronisation for any K."""
+        K = int(steps)
+        if K < 1:
+            raise ValueError(f"sweep takes steps >= 1, not {steps!r}")
         P = L.device_f64(prices, self.device)
         if P.dim() == 2:
             P = P.unsqueeze(-1)
@@ -389,10 +481,70 @@ class VectorAggregator:
             rb.hist_row.fill_(float("nan"))
         keys = (self.seeds.repeat(C), self.starts.repeat(C), eff.repeat(C))
         rb.step_episodes(*keys, hist=rb.hist_row if hold and self._row is not None else None)
+        if K > 1:
+            return self._roll(rb, C, K, Pc, on, eff, keys, hold)
         sums = rb.aggregate_groups().view(C, self.E, 3)
         if hold:
             self._hold = {"C": C, "P": Pc, "gen": self._gen, "on": on, "src": rb, "keys": keys}
         return sums.permute(1, 0, 2).contiguous()
+
+    def _roll(self, rb, C, K, Pc, on, eff, keys, hold):
+        """The rest of a K-step sweep after the replicas' step 0: its sums, the held copy of it, then steps
+        1 .. K - 1 of the replicas, each step's sums written in place into block j of the [K][C * E][3] buffer
+        kept per (C, K).  The clock rows are fixed-shape ops: no host synchronisation."""
+        E, T = self.E, self.num_timesteps
+        buf = self._path_sums.get((C, K))
+        if buf is None:
+            buf = self._path_sums[(C, K)] = torch.zeros((K, C * E, 3), dtype=torch.float64, device=self.device)
+        rb.aggregate_groups(out=buf[0])
+        src = rb
+        if hold:
+            src = self._held.get(C)
+            if src is None:
+                src = self._held[C] = HeldReplicas(rb)
+            src.fill(rb)
+        idle = torch.full_like(eff, -1)
+        for j in range(1, K):
+            clk = torch.where((eff >= 0) & (eff + j < T), eff + j, idle)
+            rb.step_episodes(keys[0], keys[1], clk.repeat(C))
+            rb.aggregate_groups(out=buf[j])
+        self.sweep_steps = torch.where(eff >= 0, (T - eff).clamp(max=K), torch.zeros_like(eff))
+        if hold:
+            self._hold = {"C": C, "P": Pc, "gen": self._gen, "on": on, "src": src, "keys": keys}
+        out = buf.view(K, C, E, 3).permute(2, 1, 0, 3).contiguous()
+        self._paths = (out, buf)
+        return out
+
+    def select_paths(self, paths, tracked, setpoints, prices, weights, max_poss_load):
+        """`select` over K-step rollouts (dragg_mpc_select_paths): per episode the candidate whose loads
+        (`paths` [E][C][K][3], `sweep(steps=K)`'s) lie closest, weighted by `weights` [K], to the setpoints the
+        environment's rule would file if the candidate were played -- from the tracked loads `tracked` [E][P],
+        the setpoints now `setpoints` [E] and the community's `max_poss_load`; only the steps an episode has
+        left count.  Ties to the smaller |price| (`prices` [E][C] or [E][C][n]: its first entry), then the
+        smaller index; -1 where no candidate has its loads or the episode is idle.  -> device int32 [E]; the
+        scores are kept in `self.path_scores` ([E][C], NaN: no score).  Device tensors are read where they are:
+        no synchronisation."""
+        dev, E = self.device, self.E
+        S = L.device_f64(paths, dev)
+        if S.dim() != 4 or S.shape[0] != E or S.shape[3] != 3:
+            raise ValueError(f"select_paths takes paths [{E}][C][K][3], not {list(S.shape)}")
+        C, K = int(S.shape[1]), int(S.shape[2])
+        last = getattr(self, "_paths", None)
+        sums = last[1] if last is not None and last[0] is paths else S.permute(2, 1, 0, 3).reshape(K, C * E, 3).contiguous()
+        P = L.device_f64(prices, dev).reshape(E, C, -1).permute(1, 0, 2).reshape(C * E, -1).contiguous()
+        w = L.device_f64(weights, dev).reshape(-1).contiguous()
+        if w.numel() != K:
+            raise ValueError(f"select_paths takes {K} weights, not {w.numel()}")
+        score = self._path_score.get(C)
+        if score is None:
+            score = self._path_score[C] = torch.full((C * E,), float("nan"), dtype=torch.float64, device=dev)
+        on = self.active()
+        ran = torch.where(on, self.clocks, torch.full_like(self.clocks, -1))
+        choice = self.batch.select_paths(sums, ran, L.device_f64(tracked, dev).reshape(E, -1).contiguous(),
+                                         L.device_f64(setpoints, dev).reshape(-1).contiguous(), w, P,
+                                         self.num_timesteps, 0.5 * float(max_poss_load), score=score)
+        self.path_scores = score.view(C, E).t()
+        return choice
 
     def select(self, sums, setpoints, prices):
         """Per episode the candidate whose load (`sums` [E][C][3], `sweep`'s) lies closest to its setpoint

@@ -464,6 +464,47 @@ int dragg_mpc_env_file(const dragg_mpc_dims* dims, const dragg_mpc_env* env, con
 int dragg_mpc_env_reset(const dragg_mpc_dims* dims, const dragg_mpc_env* env, const uint8_t* mask,
                         dragg_mpc_hash* hash, void* stream);
 
+/* The choice over K-step rollouts (since v10, additive): dragg_mpc_select_groups for candidates that were
+   rolled K steps ahead -- after dragg_mpc_replicate, K times (dragg_mpc_step_episodes at the clocks ran + j,
+   dragg_mpc_aggregate_groups into block j of `sums`).  E = max(dst_dims.n_groups, 1) episodes, `copies` = C
+   candidates each, copy-major groups c * E + e; all pointers are device pointers.
+   For episode e let t = ran[e], k = min(K, T - t) (0 if t < 0 or t >= T: the episode took no step) and, for
+   candidate c, l_j = sums[j][c * E + e][0].
+   Setpoints: s_0 = target[e]; s_j, j >= 1, is the setpoint gen_setpoint's rule returns at timestep t + j with load
+   l_(j-1) on the state the call before left -- what dragg_mpc_env_file would file if the candidate were played j
+   times, bit for bit: at timestep < 2 the tracked loads start over at fresh_load (so a rollout from t = 0 never
+   tracks l_0), later the oldest makes room for the new load; the average is summed in numpy's pairwise order and
+   divided by P.  max_load / min_load do not enter.  `tracked` is only read: the window after j steps is a
+   function of it and l_0 .. l_(j-1).
+   Score: (((0.0 + w_0 * |l_0 - s_0|) + w_1 * |l_1 - s_1|) + ...) over j < k, plain fp64 in ascending j, the
+   product rounded before the sum.  Rows j >= k of `sums` are never read.  A candidate with a NaN l_j, j < k, is
+   invalid: its score is NaN and it is never chosen.
+   Choice: the valid c of least score; ties go to the smaller |prices[c * E + e][0]|, then to the smaller c (the
+   candidates are compared in ascending c with dragg_mpc_select_groups' comparison; the doubles as they are, no
+   tolerance).  None valid, or k = 0: choice[e] = -1 and every score of e NaN.  With K = 1 and weights {1.0} the
+   choice is dragg_mpc_select_groups' for every input with ran[e] in [0, T).
+   One kernel (a block per episode, a lane per candidate); vector stores, no atomics; sums, ran, tracked, target,
+   weights and prices are only read.  n_homes == 0: every choice -1, every score NaN.  DRAGG_E_ARG: a NULL p or a
+   NULL member other than score; steps < 1; prev_timesteps outside 1 .. DRAGG_ENV_PREV_MAX; num_timesteps < 1;
+   n_rp < 1; copies < 1; n_homes % E != 0; nothing is written then. */
+typedef struct dragg_mpc_paths {
+    int32_t steps;            /* K >= 1 */
+    int32_t num_timesteps;    /* T */
+    int32_t prev_timesteps;   /* P, 1 .. DRAGG_ENV_PREV_MAX */
+    double  fresh_load;       /* max_poss_load / 2 */
+    const double*  sums;      /* [K][C*E][3], copy-major groups c*E+e: aggregate_groups' rows per rollout step */
+    const int32_t* ran;       /* [E] the clock step 0 ran with; < 0 or >= T: the episode took no step */
+    const double*  tracked;   /* [E][P] gen_setpoint's tracked loads now (oldest first); only read */
+    const double*  target;    /* [E] the setpoint now (observation row agg_setpoint) */
+    const double*  weights;   /* [K] */
+    const double*  prices;    /* [C*E][n_rp] */
+    int32_t n_rp;
+    int32_t* choice;          /* [E] */
+    double*  score;           /* optional [C*E] */
+} dragg_mpc_paths;
+int dragg_mpc_select_paths(const dragg_mpc_dims* dst_dims, int32_t copies, const dragg_mpc_paths* p,
+                           void* stream);
+
 /* Plan observations (since v10, additive): the community's planned curves per group, reduced from the hash
    arrays every successful solve leaves on the device.  A pure function of them: reads hash.vals and hash.fc
    only, writes plan.curve, plan.count and plan.stats only.  G = max(dims.n_groups, 1), Nb = n_homes / G;
