@@ -115,6 +115,33 @@ class Paths(ctypes.Structure):
                 ("weights", c_dp), ("prices", c_dp), ("n_rp", ctypes.c_int32), ("choice", c_dp), ("score", c_dp)]
 
 
+class Classes(ctypes.Structure):
+    """dragg_mpc_classes: P price classes and the community's map (device int32 [Nb], by base home)."""
+    _fields_ = [("n_classes", ctypes.c_int32), ("price_class", c_dp)]
+
+
+CLASS_MAX = 64                 # DRAGG_CLASS_MAX: the price classes a community can hold
+TYPE_CLASS_NAMES = ("base", "pv_only", "battery_only", "pv_battery")      # price_classes="type": class = home type
+
+
+def price_class_map(classes, n_homes, n_classes=None):
+    """A community's price-class map as host values: `classes` (an int sequence, one per base home) and P
+    (`n_classes`; None: the largest class + 1) -> (int32 array [n_homes], P).  ValueError for a wrong length, a
+    value outside 0 .. P - 1, or P outside 1 .. CLASS_MAX: no such map reaches the device."""
+    c = np.asarray(classes.cpu() if hasattr(classes, "cpu") else classes)
+    if c.ndim != 1 or len(c) != int(n_homes):
+        raise ValueError(f"price classes: one per base home ({n_homes}), not {list(c.shape)}")
+    if len(c) and not np.all(c == np.floor(c.astype(float))):
+        raise ValueError("price classes are integers")
+    c = c.astype(np.int64)
+    P = int(n_classes) if n_classes is not None else (int(c.max()) + 1 if len(c) else 1)
+    if not 1 <= P <= CLASS_MAX:
+        raise ValueError(f"n_classes must lie in 1..{CLASS_MAX}, not {P}")
+    if len(c) and (c.min() < 0 or c.max() >= P):
+        raise ValueError(f"price classes must lie in 0..{P - 1}, found {int(c.min())}..{int(c.max())}")
+    return c.astype(np.int32), P
+
+
 PLAN_WAYS = 16                 # DRAGG_PLAN_WAYS: the partial sums of a plan entry (part of its summation order)
 # the forecast keys a plan curve can hold (dragg_fc_key, bit k of dragg_mpc_plan.fc_keys) and the vals rows a plan
 # statistic can hold (dragg_val, bit r of val_rows), by their short names
@@ -203,7 +230,8 @@ EXPORTS = ["dragg_mpc_abi_version", "dragg_mpc_strerror", "dragg_mpc_lds_bytes",
            "dragg_mpc_side_workspace_bytes", "dragg_mpc_side_grid", "dragg_mpc_source_hash",
            "dragg_mpc_replicate", "dragg_mpc_aggregate_groups", "dragg_mpc_step_episodes",
            "dragg_mpc_season_noise_episodes", "dragg_mpc_adopt", "dragg_mpc_select_groups", "dragg_mpc_env_file",
-           "dragg_mpc_env_reset", "dragg_mpc_plan_groups", "dragg_mpc_select_paths"]
+           "dragg_mpc_env_reset", "dragg_mpc_plan_groups", "dragg_mpc_select_paths", "dragg_mpc_step_classes",
+           "dragg_mpc_plan_classes"]
 
 _LIB = None
 
@@ -277,6 +305,11 @@ def load(path=LIB_PATH):
     lib.dragg_mpc_env_reset.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Env), c_dp, ctypes.POINTER(Hash), c_dp]
     lib.dragg_mpc_plan_groups.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Hash), ctypes.POINTER(Plan), c_dp]
     lib.dragg_mpc_select_paths.argtypes = [ctypes.POINTER(Dims), ctypes.c_int32, ctypes.POINTER(Paths), c_dp]
+    lib.dragg_mpc_step_classes.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Problem), ctypes.POINTER(Episodes),
+                                           ctypes.POINTER(Classes), ctypes.POINTER(Hash), ctypes.POINTER(Out),
+                                           ctypes.c_int32, c_dp, c_dp]
+    lib.dragg_mpc_plan_classes.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Hash), ctypes.POINTER(Classes),
+                                           ctypes.POINTER(Plan), c_dp]
     if lib.dragg_mpc_abi_version() != ABI_VERSION:
         raise DraggError("ABI version mismatch between dragg_amd and libdragg_mi355x.so")
     if not os.environ.get("DRAGG_LIB"):

@@ -1255,9 +1255,15 @@ struct KArgs {
     // groups' own seeds, start indices and clocks, each [G] or NULL: the shared value (PM_GROUPED kernels; all
     // NULL, as KArgs{} leaves them: a grouped dragg_mpc_step).
     // One slot for both keeps the kernels' argument block, and with it the code of every other kernel, as it was
+    // Beside ep, in the room ex leaves: the community's price classes (dragg_mpc_step_classes; price_class NULL: none,
+    // one price row per group).  Only the PM_CLASSES prologue reads them
     union {
         dragg_mpc_explicit ex;
-        dragg_mpc_episodes ep;
+        struct {
+            dragg_mpc_episodes ep;
+            const int32_t* price_class;    // [Nb] by base home (PM_CLASSES kernels; NULL otherwise)
+            int32_t n_classes;             // P, 2 .. DRAGG_CLASS_MAX
+        };
     };
     double* vals;
     double* fc;
@@ -1277,7 +1283,8 @@ struct KArgs {
     long long step_work_cap;   // ... its work bound per pass (0: STEP_WORK_CAP)
     int narrow_lds;        // the step-function launch's LDS bytes per block (0: all a CU has, narrow_layout)
 };
-static_assert(sizeof(dragg_mpc_episodes) <= sizeof(dragg_mpc_explicit), "KArgs: ep shares ex's slot");
+static_assert(sizeof(dragg_mpc_episodes) + sizeof(const int32_t*) + sizeof(int32_t) <= sizeof(dragg_mpc_explicit),
+              "KArgs: ep and the price classes share ex's slot");
 
 // a clock value the side pass wrote: the reader must acquire before it reads the home's rows
 constexpr int LAG_SIDE = 1 << 30;
@@ -1305,7 +1312,12 @@ DEV void lag_finish(const KArgs& a, int home) {
 // problem arrays, explicit per-home inputs (dragg_mpc_solve_explicit), or a step of a grouped batch
 // (PM_GROUPED: dragg_mpc_step with dims.n_groups > 1 and dragg_mpc_step_episodes, whose groups may each
 // have their own noise seed, start index and clock)
-constexpr int PM_STEP = 0, PM_EXPLICIT = 1, PM_GROUPED = 2;
+constexpr int PM_STEP = 0, PM_EXPLICIT = 1, PM_GROUPED = 2, PM_CLASSES = 3;
+// PM_CLASSES (dragg_mpc_step_classes with P > 1): PM_GROUPED with the price row picked by the home's price class.
+// An instantiation of its own, so that the kernels of a grouped batch without classes stay as they were to the
+// instruction (folded into PM_GROUPED behind a NULL check, the lookup cost the two-chunk hot kernel 2 % through
+// register allocation alone: 220 against 215 us at 160 homes, profiles/r15/classes/)
+constexpr bool pm_grouped(int PM) { return PM == PM_GROUPED || PM == PM_CLASSES; }
 
 // PM_GROUPED: the group of a home (G consecutive replicas of N / G base homes), its base home and the three
 // values of the group's own, each the shared one where a.ep's member is NULL.  The group is the same for the
@@ -1361,21 +1373,29 @@ DEV int prologue(const KArgs& a, Home& h, const Lds& L, const Io& io, int lane, 
 #pragma clang fp contract(off)   // draw sizes, Tw0 mixing and the season test as in numpy
         // (a grouped batch: the group's own clock, start index and seed in place of the shared ones)
         Group grp{};
-        if (PM == PM_GROUPED) grp = group_of(a, home);
-        const int t = PM == PM_GROUPED ? grp.t : a.t;
+        if (pm_grouped(PM)) grp = group_of(a, home);
+        const int t = pm_grouped(PM) ? grp.t : a.t;
         h.t = t;
         const int dt = h.dt;
         const int lag = H / dt + 1;                           // mpc_calc.py:194
         const int nraw = lag * dt;
         const int base_hour = t / dt;
-        const int s0 = (PM == PM_GROUPED ? grp.start : a.p.start_index) + t;
+        const int s0 = (pm_grouped(PM) ? grp.start : a.p.start_index) + t;
         // a grouped batch (dims.n_groups = G: G consecutive replicas of N / G base homes): the home
         // reads its group's price row and draws its base home's noise.  Both are the same for the whole
-        // block (group_of), so they stay in scalar registers
+        // block (group_of), so they stay in scalar registers.  With price classes (PM_CLASSES) the group has
+        // P rows and the home reads its class's: base home -> class -> row, block-uniform still; the class
+        // is clamped into 0 .. P - 1, so no device data can point past the price rows
         const double* rpl = a.p.reward_price;
         int nhome = home;
         if (PM == PM_GROUPED) {
             rpl += (size_t)grp.g * a.d.n_rp;
+            nhome = (int)grp.base;
+        }
+        if (PM == PM_CLASSES) {
+            const int P = a.n_classes;
+            const int cls = __builtin_amdgcn_readfirstlane(min(max(a.price_class[grp.base], 0), P - 1));
+            rpl += ((size_t)grp.g * P + (unsigned)cls) * a.d.n_rp;
             nhome = (int)grp.base;
         }
         auto rawv = [&](int idx) -> double {                  // np.repeat(list, dt) / dt
@@ -1401,7 +1421,7 @@ DEV int prologue(const KArgs& a, Home& h, const Lds& L, const Io& io, int lane, 
             if (a.noise) z = a.noise[(size_t)k * N + home];
             else {
                 double z0, z1;
-                normal_pair(PM == PM_GROUPED ? grp.seed : a.p.seed, a.p.home_offset + nhome * max(a.p.home_stride, 1), t, k >> 1, &z0, &z1);
+                normal_pair(pm_grouped(PM) ? grp.seed : a.p.seed, a.p.home_offset + nhome * max(a.p.home_stride, 1), t, k >> 1, &z0, &z1);
                 z = (k & 1) ? z1 : z0;
             }
             mx = fmax(mx, a.p.oat[s0 + k + 1] + pow(1.1, (double)k) * z);
@@ -1466,7 +1486,7 @@ __global__ __launch_bounds__(64) void mpc_home_kernel(KArgs a) {
     const int lane = threadIdx.x;
     const int N = a.d.n_homes;
     if (home >= N) return;
-    if constexpr (PM == PM_GROUPED)             // an idle group's blocks leave before any write
+    if constexpr (pm_grouped(PM))               // an idle group's blocks leave before any write
         if (group_idle(a, group_of(a, home))) return;
     Home h;
     const int H = a.d.horizon;
@@ -4867,7 +4887,7 @@ __global__ __launch_bounds__(WAVE * NW, MODE == DM_FRONT ? (ILP > 1 ? 2 : 3) : M
         if (home >= N) return;
         // an idle group's blocks leave before any write; every later launch works off the lists this one
         // fills, so none of them sees an idle home
-        if constexpr (PM == PM_GROUPED)
+        if constexpr (pm_grouped(PM))
             if (group_idle(a, group_of(a, home))) return;
         if (a.clk) {
             // lag mode, main pass: a home whose previous step is not complete yet goes to the side pass
@@ -5371,7 +5391,11 @@ struct PlanArgs {
     unsigned char key[DRAGG_NFC];       // the chosen keys, ascending
     unsigned char row[DRAGG_NVAL];      // the chosen rows, ascending
 };
-__global__ __launch_bounds__(PLAN_NT) void plan_groups_kernel(PlanArgs a) {
+// CLS (dragg_mpc_plan_classes): the block reduces class `cls_c` of its group alone -- a home of another class is
+// loaded as NaN (absent: its counter too, so nothing of its fc block is read), which leaves every add of the
+// class's own homes where plan_groups has it.  The class of home i is cls[i] (by base home), clamped into 0 .. P - 1
+template <bool CLS>
+DEV void plan_body(const PlanArgs& a, const int32_t* cls, int P, int cls_c) {
 #pragma clang fp contract(off)
     __shared__ double p_sum[DRAGG_PLAN_WAYS][WAVE], p_min[DRAGG_PLAN_WAYS][WAVE], p_max[DRAGG_PLAN_WAYS][WAVE];
     __shared__ int p_cnt[DRAGG_PLAN_WAYS][WAVE];
@@ -5394,11 +5418,18 @@ __global__ __launch_bounds__(PLAN_NT) void plan_groups_kernel(PlanArgs a) {
     if (live) {
         for (int i0 = w; i0 < Nb; i0 += DRAGG_PLAN_WAYS * PLAN_UNROLL) {
             double v[PLAN_UNROLL];
+            bool in[PLAN_UNROLL];           // the home is of this block's class (no classes: every home)
+#pragma unroll
+            for (int u = 0; u < PLAN_UNROLL; ++u) {
+                const int i = i0 + u * DRAGG_PLAN_WAYS;
+                in[u] = true;
+                if constexpr (CLS) in[u] = i < Nb && min(max(cls[i], 0), P - 1) == cls_c;
+            }
             if (j == 0) {
 #pragma unroll
                 for (int u = 0; u < PLAN_UNROLL; ++u) {
                     const int i = i0 + u * DRAGG_PLAN_WAYS;
-                    v[u] = i < Nb ? v0[i] : nan;
+                    v[u] = i < Nb && in[u] ? v0[i] : nan;
                 }
             } else {
                 // two rounds of independent loads: the homes' counters, then their values (a home past the
@@ -5407,7 +5438,7 @@ __global__ __launch_bounds__(PLAN_NT) void plan_groups_kernel(PlanArgs a) {
 #pragma unroll
                 for (int u = 0; u < PLAN_UNROLL; ++u) {
                     const int i = i0 + u * DRAGG_PLAN_WAYS;
-                    cnt[u] = i < Nb ? cn[i] : nan;
+                    cnt[u] = i < Nb && in[u] ? cn[i] : nan;
                 }
 #pragma unroll
                 for (int u = 0; u < PLAN_UNROLL; ++u) {
@@ -5448,17 +5479,23 @@ __global__ __launch_bounds__(PLAN_NT) void plan_groups_kernel(PlanArgs a) {
         mn = p_min[m][lane] < mn ? p_min[m][lane] : mn;
         mx = p_max[m][lane] > mx ? p_max[m][lane] : mx;
     }
+    const size_t og = CLS ? (size_t)g * P + cls_c : (size_t)g;         // the output's (group, class) row
     if (rows) {
-        double* o = a.stats + ((size_t)g * a.nr + e) * 4;
+        double* o = a.stats + (og * a.nr + e) * 4;
         o[0] = (double)n;
         o[1] = t[0];
         o[2] = mn;
         o[3] = mx;
     } else {
-        const size_t o = (size_t)g * a.nk * H + e;
+        const size_t o = og * a.nk * H + e;
         a.curve[o] = t[0];
         a.count[o] = n;
     }
+}
+__global__ __launch_bounds__(PLAN_NT) void plan_groups_kernel(PlanArgs a) { plan_body<false>(a, nullptr, 1, 0); }
+// grid (entry blocks, G, P): block (x, g, c) is plan_groups' block (x, g) on class c's homes
+__global__ __launch_bounds__(PLAN_NT) void plan_classes_kernel(PlanArgs a, const int32_t* cls, int P) {
+    plan_body<true>(a, cls, P, (int)blockIdx.z);
 }
 
 // (nb: the base homes of a grouped batch, N otherwise.  Home r of group g = r / nb draws the stream of
@@ -5577,7 +5614,8 @@ int hot_ilp(int dev, int N) {
 // The launches of a step, each described once: its kernel (the PM instantiation), its threads per block and
 // its dynamic LDS bytes, from the dims and the knobs.  The serial step, both lag passes, mid_slots and
 // dragg_mpc_kernel_info_get all read them here.  Three instantiations: PM_STEP (an ordinary step, lag mode),
-// PM_EXPLICIT, and PM_GROUPED for every grouped batch (a price sweep and a batch of episodes alike).
+// PM_EXPLICIT, PM_GROUPED for every grouped batch (a price sweep and a batch of episodes alike), and PM_CLASSES
+// for a grouped batch with price classes.
 struct Launch { const void* kern; int nt; size_t lds; };
 struct Launches {
     Launch home;          // relax / round_lp: the whole solve, one workgroup per home
@@ -5866,6 +5904,38 @@ int dragg_mpc_step_episodes(const dragg_mpc_dims* dims, const dragg_mpc_problem*
     a.noise = noise;
     a.ep = *ep;
     return launch<PM_GROUPED>(a, (hipStream_t)stream);
+}
+
+// the class arguments' own check (both class entries): 0 = none in effect (NULL or P <= 1 after the range check:
+// the entry is its plain twin), 1 = classes, < 0 = DRAGG_E_ARG
+static int classes_in_effect(const dragg_mpc_classes* classes) {
+    if (!classes) return 0;
+    if (classes->n_classes < 1 || classes->n_classes > DRAGG_CLASS_MAX) return DRAGG_E_ARG;
+    if (classes->n_classes == 1) return 0;
+    return classes->price_class ? 1 : DRAGG_E_ARG;
+}
+
+// dragg_mpc_step_episodes with P price rows per group: the same launches with the PM_CLASSES kernels, the class
+// map beside a.ep
+int dragg_mpc_step_classes(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, const dragg_mpc_episodes* ep,
+                           const dragg_mpc_classes* classes, dragg_mpc_hash* hash, dragg_mpc_out* out,
+                           int32_t timestep, const double* noise, void* stream) {
+    const int cls = classes_in_effect(classes);
+    if (cls < 0) return DRAGG_E_ARG;
+    if (!cls) return dragg_mpc_step_episodes(dims, prob, ep, hash, out, timestep, noise, stream);
+    if (!ep || !prob) return DRAGG_E_ARG;
+    dragg_mpc_problem p = *prob;
+    if (ep->start_index) p.start_index = 0;
+    KArgs a;
+    const int rc = solve_args(dims, &p, hash, out, ep->timestep ? 0 : timestep, true, &a);
+    if (rc || dims->n_homes == 0) return rc;
+    a.p = *prob;
+    a.t = timestep;
+    a.noise = noise;
+    a.ep = *ep;
+    a.price_class = classes->price_class;
+    a.n_classes = classes->n_classes;
+    return launch<PM_CLASSES>(a, (hipStream_t)stream);
 }
 
 // one pass of a lag-mode step: solve_args, then what only lag mode needs
@@ -6171,8 +6241,9 @@ int dragg_mpc_select_paths(const dragg_mpc_dims* dst_dims, int32_t copies, const
     return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
 }
 
-int dragg_mpc_plan_groups(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, const dragg_mpc_plan* plan,
-                          void* stream) {
+// both plan entries: cls NULL = dragg_mpc_plan_groups, else P >= 2 classes on the grid's z
+static int plan_launch(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, const dragg_mpc_plan* plan,
+                       const int32_t* cls, int P, void* stream) {
     if (!dims || !hash || !plan || dims->n_homes < 0 || dims->horizon < 1) return DRAGG_E_ARG;
     if ((plan->fc_keys >> DRAGG_NFC) != 0 || (plan->val_rows >> DRAGG_NVAL) != 0) return DRAGG_E_ARG;
     const int G = group_count(dims);
@@ -6198,8 +6269,24 @@ int dragg_mpc_plan_groups(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash
     const long long blocks = (entries + WAVE - 1) / WAVE + (a.nr ? 1 : 0);
     if (blocks > 0x7FFFFFFFLL) return DRAGG_E_ARG;
     a.curve_blocks = (int)((entries + WAVE - 1) / WAVE);
-    hipLaunchKernelGGL(plan_groups_kernel, dim3((unsigned)blocks, (unsigned)G), dim3(PLAN_NT), 0, (hipStream_t)stream, a);
+    if (cls)
+        hipLaunchKernelGGL(plan_classes_kernel, dim3((unsigned)blocks, (unsigned)G, (unsigned)P), dim3(PLAN_NT), 0,
+                           (hipStream_t)stream, a, cls, P);
+    else
+        hipLaunchKernelGGL(plan_groups_kernel, dim3((unsigned)blocks, (unsigned)G), dim3(PLAN_NT), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+}
+
+int dragg_mpc_plan_groups(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, const dragg_mpc_plan* plan,
+                          void* stream) {
+    return plan_launch(dims, hash, plan, nullptr, 1, stream);
+}
+
+int dragg_mpc_plan_classes(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, const dragg_mpc_classes* classes,
+                           const dragg_mpc_plan* plan, void* stream) {
+    const int cls = classes_in_effect(classes);
+    if (cls < 0) return DRAGG_E_ARG;
+    return plan_launch(dims, hash, plan, cls ? classes->price_class : nullptr, cls ? classes->n_classes : 1, stream);
 }
 
 }  // extern "C"

@@ -148,6 +148,7 @@ class MPCBatch:
                              tou if tou is not None else [0.0], start_index)
         self.workspace = None
         self.lag = None
+        self.n_classes, self.price_class, self.price_class_host = 1, None, None    # (set_price_classes)
         self.set_reward_price(reward_price)
         self.vals = torch.full((L.NVAL, self.N), float("nan"), dtype=torch.float64, device=dev)
         # the forecast fields <key>_<j>: stored home-contiguous ([N][NFC][H], dragg_mi355x.h: one home's
@@ -187,7 +188,24 @@ class MPCBatch:
         (e.g. an RL action broadcast over RCCL), taken without a host round trip.  A grouped batch
         takes [G][n], one list per group (every row n entries), or one list for every group."""
         G = getattr(self, "groups", 1)
-        if G > 1:
+        P = getattr(self, "n_classes", 1)
+        if P > 1:
+            # price classes: P rows per group, [G][P][n] on the device.  [G][P] (class scalars; a 2-D tensor of
+            # that shape always means this) or [G][P][n], or one [P] / [P][n] for every group
+            rp = L.device_f64(rp, self.device)
+            shape = tuple(rp.shape)
+            if shape == (G, P):
+                rp = rp.reshape(G, P, 1)
+            elif shape == (P,):
+                rp = rp.reshape(1, P, 1).expand(G, P, 1)
+            elif len(shape) == 2 and shape[0] == P:
+                rp = rp.reshape(1, P, -1).expand(G, P, -1)
+            if rp.dim() != 3 or tuple(rp.shape[:2]) != (G, P) or rp.shape[2] < 1:
+                raise ValueError(f"a batch of {G} groups and {P} price classes takes reward prices [{G}][{P}], "
+                                 f"[{G}][{P}][n], [{P}] or [{P}][n], not {list(shape)}")
+            n = rp.shape[2]
+            rp = rp.reshape(-1).contiguous()
+        elif G > 1:
             rp = L.device_f64(rp, self.device)
             if rp.dim() < 2:
                 rp = rp.reshape(1, -1).expand(G, -1)
@@ -211,6 +229,31 @@ class MPCBatch:
         self.dims.n_rp = n
         if self.workspace is not None or hasattr(self, "vals"):
             self._ensure_workspace()
+
+    def set_price_classes(self, classes, n_classes=None):
+        """The community's price classes (dragg_mpc_classes): `classes`, a host int sequence [Nb], gives every
+        base home a class 0 .. P - 1 (`n_classes` = P; None: the largest class + 1), shared by every group.  The
+        batch then holds P reward-price rows per group (`set_reward_price`: [G][P], [G][P][n], or one [P] /
+        [P][n] for every group) and `step_episodes` solves home r of group g under row (g, classes[r % Nb])
+        (dragg_mpc_step_classes); state has no class, so `replicate_from` / `adopt_from` are as before.  The rows
+        start over at price 0.  Like a grouped batch, a batch with P > 1 has no lag mode and no explicit solves;
+        `step_episodes` is its solve.  ValueError: a wrong length, a class outside 0 .. P - 1, P outside
+        1 .. CLASS_MAX -- no such map reaches the device.  P == 1 (or classes None): no classes."""
+        if classes is None:
+            cm, P = None, 1
+        else:
+            cm, P = L.price_class_map(classes, self.Nb, n_classes)
+        if P > 1 and getattr(self, "lag", None) is not None:
+            raise ValueError("a batch in lag mode takes no price classes")
+        self.n_classes = P
+        self.price_class_host = cm if P > 1 else None
+        self.price_class = (torch.tensor(cm, dtype=torch.int32, device=self.device).contiguous() if P > 1 else None)
+        self.set_reward_price(torch.zeros((max(getattr(self, "groups", 1), 1), P) if P > 1
+                                          else (max(getattr(self, "groups", 1), 1), 1), dtype=torch.float64))
+
+    def _classes(self):
+        """The dragg_mpc_classes struct of this batch's map."""
+        return L.Classes(n_classes=int(self.n_classes), price_class=L.ptr(self.price_class))
 
     def _ensure_workspace(self):
         """Device scratch of dragg_mpc_workspace_bytes(dims) bytes (it grows when a reward-price list makes
@@ -285,6 +328,8 @@ class MPCBatch:
     # ------------------------------------------------------------------ launches
     def step(self, t, noise=None, hist=None, stream=None):
         """One closed-loop timestep for every home (run_iteration, aggregator.py:711-726)."""
+        if self.n_classes > 1:
+            raise ValueError("a batch with price classes is stepped by step_episodes (dragg_mpc_step_classes)")
         with torch.cuda.device(self.device):
             self.drain(stream)
             if self.lag is not None:
@@ -309,8 +354,8 @@ class MPCBatch:
         step t), the side stream and the events that order the two passes."""
         if self.dims.int_mode not in (L.INT_ROUND, L.INT_FAIL):
             raise ValueError("lag mode needs int_mode 'round' (or 'fail')")
-        if self.groups > 1:
-            raise ValueError("a grouped batch has no lag mode (dragg_mpc_step only)")
+        if self.groups > 1 or self.n_classes > 1:
+            raise ValueError("a grouped batch, or one with price classes, has no lag mode (dragg_mpc_step only)")
         dev = self.device
         with torch.cuda.device(dev):
             self.lag = {
@@ -387,6 +432,8 @@ class MPCBatch:
     def solve_explicit(self, t, T0, Tw0, E0, counter, winter, draw, oat, ghi, price, stream=None):
         """Independent per-home solves with explicit inputs ([N] and [H+1 or H][N] arrays)."""
         dev, N, H = self.device, self.N, self.H
+        if self.n_classes > 1:
+            raise ValueError("a batch with price classes takes no explicit inputs (they carry no price list)")
 
         def d(x, shape, dtype=torch.float64):
             return torch.as_tensor(np.asarray(x), dtype=dtype).to(dev).reshape(shape).contiguous()
@@ -531,7 +578,7 @@ class MPCBatch:
             return out
 
     # ------------------------------------------------------------------ plan observations
-    def plan_groups(self, keys, rows=(), out=None, stream=None, src=None):
+    def plan_groups(self, keys, rows=(), out=None, stream=None, src=None, classes=False):
         """The planned curves of every group (dragg_mpc_plan_groups) -> (curve [G][nk][H] float64, count
         [G][nk][H] int32, stats [G][nr][4] float64: count, sum, min, max) as device tensors.  `keys`: the forecast
         keys whose time-aligned horizon curve is summed over each group's homes, `rows`: the vals rows whose
@@ -542,14 +589,19 @@ class MPCBatch:
         sums over homes w, w + 16, ..., then a balanced tree: `vector.plan_groups_reference`), so a group's rows
         do not depend on the batch around it.  The hash arrays are only read.  `out`: a (curve, count, stats)
         triple to write into instead of new tensors; `src`: another holder of hash arrays of this horizon (vals,
-        fc_store, N, groups -- a held sweep's replicas) in place of this batch's.  No synchronisation."""
+        fc_store, N, groups -- a held sweep's replicas) in place of this batch's.  No synchronisation.
+        classes=True: per (group, price class) of this batch's map (dragg_mpc_plan_classes) -> curve and count
+        [G][P][nk][H], stats [G][P][nr][4]; class c's rows are the group's rows with every home of another class
+        absent (`vector.plan_classes_reference`), an empty class's the empty result.  Without a map (P == 1) the
+        class axis has length 1 and the rows are plan_groups' own."""
         km, rm, ki, ri = L.plan_select(keys, rows)
         b = self if src is None else src
         G = max(int(getattr(b, "groups", 1)), 1)
         if b.H != self.H:
             raise ValueError(f"plan_groups: a source of horizon {b.H}, not {self.H}")
-        shapes = {"curve": ((G, len(ki), self.H), torch.float64), "count": ((G, len(ki), self.H), torch.int32),
-                  "stats": ((G, len(ri), len(L.PLAN_STATS)), torch.float64)}
+        lead = (G, int(self.n_classes)) if classes else (G,)
+        shapes = {"curve": (lead + (len(ki), self.H), torch.float64), "count": (lead + (len(ki), self.H), torch.int32),
+                  "stats": (lead + (len(ri), len(L.PLAN_STATS)), torch.float64)}
         with torch.cuda.device(self.device):
             if out is None:
                 out = tuple(torch.empty(s, dtype=d, device=self.device) for s, d in shapes.values())
@@ -562,8 +614,11 @@ class MPCBatch:
             dims = L.Dims.from_buffer_copy(self.dims)
             dims.n_homes, dims.n_groups = int(b.N), G if G > 1 else 0
             plan = L.Plan(fc_keys=km, val_rows=rm, curve=L.ptr(out[0]), count=L.ptr(out[1]), stats=L.ptr(out[2]))
-            L.check(self.lib.dragg_mpc_plan_groups(dims, L.Hash(vals=L.ptr(b.vals), fc=L.ptr(b.fc_store)), plan,
-                                                   L.stream_ptr(stream, self.device)))
+            h = L.Hash(vals=L.ptr(b.vals), fc=L.ptr(b.fc_store))
+            if classes:
+                L.check(self.lib.dragg_mpc_plan_classes(dims, h, self._classes(), plan, L.stream_ptr(stream, self.device)))
+            else:
+                L.check(self.lib.dragg_mpc_plan_groups(dims, h, plan, L.stream_ptr(stream, self.device)))
             self._keep = (src, out)
             return tuple(out)
 
@@ -635,8 +690,12 @@ class MPCBatch:
             if noise is not None:
                 noise = noise.to(device=self.device, dtype=torch.float64).contiguous()
                 assert tuple(noise.shape) == (self.H, self.N)
-            self._call(self.lib.dragg_mpc_step_episodes, self._problem(), ep, self._hash(), self._out(hist), int(t),
-                       L.ptr(noise), stream=stream)
+            if self.n_classes > 1:
+                self._call(self.lib.dragg_mpc_step_classes, self._problem(), ep, self._classes(), self._hash(),
+                           self._out(hist), int(t), L.ptr(noise), stream=stream)
+            else:
+                self._call(self.lib.dragg_mpc_step_episodes, self._problem(), ep, self._hash(), self._out(hist), int(t),
+                           L.ptr(noise), stream=stream)
             self._keep = (noise, hist, keep)
             return self.status
 

@@ -196,6 +196,9 @@ class VectorEnv:
         self.va = va = vector_aggregator
         self.config = config
         self.E, self.T = va.E, va.num_timesteps
+        # price classes (the aggregator's `price_classes`): actions are then [E][P] or [E][P][n], candidates
+        # [E][C][P] or [E][C][P][n]
+        self.n_classes, self.class_names = getattr(va, "n_classes", 1), getattr(va, "class_names", None)
         self.prev_timesteps = config["agg"]["rl"]["prev_timesteps"]
         self.max_poss_load = (sum(I.max_load(h) for h in va.homes) if max_poss_load is None else max_poss_load)
         self.n_homes = va.Nb if n_homes is None else int(n_homes)
@@ -281,11 +284,15 @@ class VectorEnv:
             C = paths.shape[1]
             P = int(self.prev_timesteps)
             fresh = [0.5 * self.max_poss_load] * P
+            if self.n_classes > 1:                   # (the tie rule's key over the classes, as the device path's)
+                rows = self.va.tie_key(candidates, C).cpu().numpy().reshape(C, self.E, 1)
+            else:
+                rows = np.asarray(candidates.cpu() if hasattr(candidates, "cpu") else candidates, dtype=float) \
+                    .reshape(self.E, C, -1).transpose(1, 0, 2)
             ch, score = select_paths_reference(
                 paths.transpose(2, 1, 0, 3).reshape(K, C * self.E, 3), np.where(on, self.timestep, -1),
                 [fresh if sp is None else sp[0] for sp in self._sp], self.agg_setpoint, _path_weights(K, weights),
-                np.asarray(candidates.cpu() if hasattr(candidates, "cpu") else candidates, dtype=float)
-                .reshape(self.E, C, -1).transpose(1, 0, 2), self.T, self.max_poss_load)
+                rows, self.T, self.max_poss_load)
             self.scores = score.reshape(C, self.E).T.copy()
             choice = torch.as_tensor(ch, dtype=torch.int32, device=self.va.device)
         else:
@@ -322,7 +329,13 @@ class DeviceVectorEnv:
     `plan_count` [E][nk][H] (int32: the homes behind each entry) and `plan_stats` [E][nr][4] (count, sum, min, max
     of each vals row), views like the others.  It is the open-loop plan of the episodes' last solves: a parked or
     finished episode keeps its last step's, a fresh one's is empty (count 0).  Without them the environment issues
-    exactly the launches it issued before."""
+    exactly the launches it issued before.
+
+    Price classes (an aggregator built with `price_classes`; `n_classes`, `class_names`): actions are [E][P] or
+    [E][P][n], candidates [E][C][P] or [E][C][P][n].  With plan keys or rows as well, one launch more per `reset`,
+    `step` and `step_swept` (dragg_mpc_plan_classes) adds `class_plan` [E][P][nk][H], `class_plan_count` (int32)
+    and `class_stats` [E][P][nr][4]: the plan observations per price class, the vector observation that answers a
+    vector action.  Without classes the launches are exactly those above."""
 
     def __init__(self, vector_aggregator, config, max_poss_load=None, n_homes=None, plan_keys=(), plan_rows=()):
         from . import _lib as L
@@ -330,6 +343,7 @@ class DeviceVectorEnv:
         self.va = va = vector_aggregator
         self.config = config
         self.E, self.T = va.E, va.num_timesteps
+        self.n_classes, self.class_names = getattr(va, "n_classes", 1), getattr(va, "class_names", None)
         self.prev_timesteps = config["agg"]["rl"]["prev_timesteps"]
         self.max_poss_load = (sum(I.max_load(h) for h in va.homes) if max_poss_load is None else max_poss_load)
         self.n_homes = va.Nb if n_homes is None else int(n_homes)
@@ -338,23 +352,32 @@ class DeviceVectorEnv:
         self._w = {}
         _, _, ki, ri = L.plan_select(plan_keys, plan_rows)
         self.plan_key_names, self.plan_row_names = [L.PLAN_KEYS[k] for k in ki], [L.PLAN_ROWS[r] for r in ri]
-        self._plan = None
+        self._plan = self._class_plan = None
         if ki or ri:
             import torch
             curve, stats = L.plan_shape(ki, ri, self.E, va.H)
             self._plan = (torch.zeros(curve, dtype=torch.float64, device=va.device),
                           torch.zeros(curve, dtype=torch.int32, device=va.device),
                           torch.zeros(stats, dtype=torch.float64, device=va.device))
+            if self.n_classes > 1:
+                curve, stats = ((s[0], self.n_classes) + s[1:] for s in (curve, stats))
+                self._class_plan = (torch.zeros(curve, dtype=torch.float64, device=va.device),
+                                    torch.zeros(curve, dtype=torch.int32, device=va.device),
+                                    torch.zeros(stats, dtype=torch.float64, device=va.device))
 
     def _observe_plan(self):
         if self._plan is not None:
             self.va.plan(self.plan_key_names, self.plan_row_names, out=self._plan)
+        if self._class_plan is not None:
+            self.va.plan(self.plan_key_names, self.plan_row_names, out=self._class_plan, classes=True)
 
     def observations(self):
         from ._lib import OBS_KEYS
         obs = {k: self.state.obs[i] for i, k in enumerate(OBS_KEYS)}
         if self._plan is not None:
             obs["plan"], obs["plan_count"], obs["plan_stats"] = self._plan
+        if self._class_plan is not None:
+            obs["class_plan"], obs["class_plan_count"], obs["class_stats"] = self._class_plan
         return obs
 
     def reset(self, mask=None, seeds=None, start_indices=None):
@@ -490,20 +513,22 @@ class SweepAgent:
         p = self.train(env) / self.scale
         return Candidate(self.index, p) if self.commit else p
 
-    def act_vector(self, env_obs):
+    def act_vector(self, env_obs, classes=None):
         """Observations of a `VectorEnv` -> candidate prices [E][C] for `VectorEnv.step_swept` (every episode
-        the same `candidates()`)."""
+        the same `candidates()`).  classes=P (an environment with P price classes): [E][C][P], every class
+        getting the same grid value -- the class path driven by this policy, the uniform prices it would play."""
         E = len(np.asarray(env_obs["agg_setpoint"]).reshape(-1))
-        return np.tile(self.candidates() / self.scale, (E, 1))
+        c = np.tile(self.candidates() / self.scale, (E, 1))
+        return c if classes is None else np.repeat(c[:, :, None], int(classes), axis=2)
 
-    def act_device(self, env_obs):
-        """`act_vector` for a `DeviceVectorEnv`: the tiled candidates as a device tensor [E][C] (built once per
-        shape and device)."""
+    def act_device(self, env_obs, classes=None):
+        """`act_vector` for a `DeviceVectorEnv`: the tiled candidates as a device tensor [E][C], or [E][C][P]
+        with classes=P (built once per shape and device)."""
         import torch
         s = env_obs["agg_setpoint"]
-        key = (int(s.numel()), s.device)
+        key = (int(s.numel()), s.device, classes)
         if getattr(self, "_tiled", None) is None or self._tiled[0] != key:
-            self._tiled = (key, torch.as_tensor(np.tile(self.candidates() / self.scale, (key[0], 1)),
+            self._tiled = (key, torch.as_tensor(self.act_vector({"agg_setpoint": np.zeros(key[0])}, classes),
                                                 dtype=torch.float64).to(s.device))
         return self._tiled[1]
 

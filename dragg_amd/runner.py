@@ -214,12 +214,17 @@ class Aggregator:
             self.config["agg"]["rl"]["prev_timesteps"] if fresh else None)
         return self.avg_load
 
-    def rl_vector(self, episodes, seeds=None, start_indices=None, device_env=False, plan_keys=(), plan_rows=()):
+    def rl_vector(self, episodes, seeds=None, start_indices=None, device_env=False, plan_keys=(), plan_rows=(),
+                  price_classes=None):
         """A vector environment of `episodes` independent runs of the loaded community (`get_homes`), all
         stepped as one grouped batch (dragg_amd.vector.VectorAggregator, rl.VectorEnv): default seeds
         `simulation.random_seed + e`, default start indices the config's own.  device_env=True: an
         `rl.DeviceVectorEnv` (observations, done flags and choices stay on the device); `plan_keys` /
-        `plan_rows`: its plan observations (device_env=True only).  One rank only."""
+        `plan_rows`: its plan observations (device_env=True only).  `price_classes`: a reward price per class of
+        homes -- "type" (class = home type: base 0, pv_only 1, battery_only 2, pv_battery 3; P = 4 even if a type is
+        absent) or an int sequence, one class per loaded home in `all_homes`' order (default: the config's
+        `rl.utility.price_classes`, else none); actions and candidates then take the class shapes of
+        `VectorAggregator`.  One rank only."""
         from .rl import DeviceVectorEnv, VectorEnv
         from .vector import VectorAggregator
         if self.world > 1:
@@ -229,10 +234,20 @@ class Aggregator:
         E = int(episodes)
         seed = int(self.config["simulation"]["random_seed"])
         checked, oat, ghi, tou = self._checked_community()
+        if price_classes is None:
+            price_classes = ((self.config.get("rl") or {}).get("utility") or {}).get("price_classes")
+        n_classes = None
+        if price_classes is not None and not isinstance(price_classes, str):
+            # one class per loaded home: P from the whole list, the map for the checked homes
+            from ._lib import price_class_map
+            pc, n_classes = price_class_map(list(price_classes), len(self.all_homes))
+            price_classes = [int(c) for c, h in zip(pc, self.all_homes)
+                             if self.check_type == "all" or h["type"] == self.check_type]
         va = VectorAggregator(checked, oat, ghi, tou, E,
                               [seed + e for e in range(E)] if seeds is None else seeds,
                               [self.start_hour_index] * E if start_indices is None else start_indices,
                               self.num_timesteps, int_mode=self.int_mode, device=self.device,
+                              price_classes=price_classes, n_classes=n_classes,
                               **({"batch_cls": self.batch_cls} if self.batch_cls else {}))
         kw = dict(max_poss_load=sum(I.max_load(h) for h in self.all_homes), n_homes=len(self.all_homes))
         if not device_env:

@@ -27,6 +27,11 @@ plays the first step.
 `plan` reduces the plans the episodes' last solves left in the hash arrays to per-episode horizon curves
 (dragg_mpc_plan_groups; `plan_groups_reference` restates it, summation order included).
 
+`VectorAggregator(..., price_classes=...)` gives every home of the community a price class: an action is then a
+price per class ([E][P]), every home reads its class's row (dragg_mpc_step_classes) and `plan(classes=True)`
+reduces the plans per (episode, class) (dragg_mpc_plan_classes; `plan_classes_reference` restates it).  The
+class-c homes of an episode equal, bit for bit, the same homes of a single run under class c's prices alone.
+
 One rank only: sharding episodes over ranks is not built.
 """
 import numpy as np
@@ -232,6 +237,39 @@ def plan_groups_reference(vals, fc, G, keys, rows=()):
     return curve, count, stats
 
 
+def plan_classes_reference(vals, fc, G, classes, P, keys, rows=()):
+    """dragg_mpc_plan_classes restated (the spec its CPU and GPU tests share): `plan_groups_reference` once per
+    class on NaN-masked copies -- for class c every vals row (the solve counter included) and every fc entry of
+    the homes whose class is not c made absent.  `classes`: the community's map [Nb] by base home, shared by the
+    G groups; P classes -> (curve [G][P][nk][H] float64, count [G][P][nk][H] int32, stats [G][P][nr][4])."""
+    vals, fc = np.asarray(vals, dtype=np.float64), np.asarray(fc, dtype=np.float64)
+    G = max(int(G), 1)
+    cm, P = L.price_class_map(classes, vals.shape[1] // G, P)
+    out = []
+    for c in range(P):
+        other = np.tile(cm != c, G)
+        v, f = vals.copy(), fc.copy()
+        v[:, other] = np.nan
+        f[other] = np.nan
+        out.append(plan_groups_reference(v, f, G, keys, rows))
+    return tuple(np.stack([o[k] for o in out], axis=1) for k in range(3))
+
+
+def resolve_price_classes(price_classes, homes, n_classes=None):
+    """A community's price classes -> (map int32 [len(homes)], P, class names), or (None, 1, None) for None.
+    "type": class = home type in `_lib.TYPE_CODE`'s order (base 0, pv_only 1, battery_only 2, pv_battery 3), P = 4
+    even if a type is absent; else an int sequence, one per home (`_lib.price_class_map`'s checks)."""
+    if price_classes is None:
+        return None, 1, None
+    if isinstance(price_classes, str):
+        if price_classes != "type":
+            raise ValueError(f"price_classes is \"type\" or an int sequence, not {price_classes!r}")
+        cm, P = L.price_class_map([L.TYPE_CODE[h["type"]] for h in homes], len(homes), len(L.TYPE_CLASS_NAMES))
+        return cm, P, list(L.TYPE_CLASS_NAMES)
+    cm, P = L.price_class_map(price_classes, len(homes), n_classes)
+    return cm, P, [str(c) for c in range(P)]
+
+
 class HeldReplicas:
     """The first step of a K-step sweep, kept while its replica batch moves on: the arrays `MPCBatch.adopt_from`
     reads (`aggregator.HeldStep`'s), but allocated once and refilled with `copy_` -- an environment step never
@@ -256,7 +294,13 @@ class HeldReplicas:
 
 class VectorAggregator:
     def __init__(self, homes, oat, ghi, tou, episodes, seeds, start_indices, num_timesteps, int_mode="round",
-                 keep_history=True, device=None, batch_cls=MPCBatch, rank=0, world=1, **batch_kw):
+                 keep_history=True, device=None, batch_cls=MPCBatch, rank=0, world=1, price_classes=None,
+                 n_classes=None, **batch_kw):
+        """price_classes ("type", or an int sequence [Nb] with `n_classes` = P; default None: one price for the
+        community): the community's price classes (`resolve_price_classes`, `MPCBatch.set_price_classes`), shared by
+        every episode and every sweep replica.  With P > 1 an action is a price per class: `step` takes [E][P] or
+        [E][P][n], `sweep` [E][C][P] or [E][C][P][n] -- a 2-D `step` tensor and a 3-D `sweep` tensor then mean class
+        scalars, never price lists.  `n_classes`, `class_names` and `price_class_host` describe the map."""
         if world > 1:
             raise ValueError("VectorAggregator runs on one rank: episodes are not sharded over ranks")
         E = int(episodes)
@@ -269,6 +313,9 @@ class VectorAggregator:
         # batch_cls is injectable only so that the host logic can be exercised on the CPU with a stand-in
         # (tests/test_vector_host.py); the solver itself is MPCBatch (HIP, no fallback)
         self.batch = batch_cls(homes, oat, ghi, tou, 0, (0.0,), int_mode=int_mode, device=dev, groups=E, **batch_kw)
+        self.price_class_host, self.n_classes, self.class_names = resolve_price_classes(price_classes, homes, n_classes)
+        if self.n_classes > 1:
+            self.batch.set_price_classes(self.price_class_host, self.n_classes)
         self.H = int(self.batch.H)
         self.n_env = int(min(len(oat), len(ghi), len(tou)))
         self.seeds = torch.zeros(E, dtype=torch.int64, device=dev)
@@ -389,10 +436,17 @@ class VectorAggregator:
         """The solve of `step`: the prices published, every active episode stepped at its own clock (kept in
         `self._keep`, -1 for the others) -> the device bool [E] of the episodes that ran.  Nothing filed yet."""
         P = L.device_f64(prices, self.device)
-        if P.dim() == 1:
-            P = P.reshape(-1, 1)
-        if P.dim() != 2 or P.shape[0] != self.E:
-            raise ValueError(f"step takes prices [{self.E}] or [{self.E}][n], not {list(P.shape)}")
+        if self.n_classes > 1:
+            if P.dim() == 2:
+                P = P.unsqueeze(-1)                              # class scalars
+            if P.dim() != 3 or tuple(P.shape[:2]) != (self.E, self.n_classes):
+                raise ValueError(f"step takes class prices [{self.E}][{self.n_classes}] or "
+                                 f"[{self.E}][{self.n_classes}][n], not {list(P.shape)}")
+        else:
+            if P.dim() == 1:
+                P = P.reshape(-1, 1)
+            if P.dim() != 2 or P.shape[0] != self.E:
+                raise ValueError(f"step takes prices [{self.E}] or [{self.E}][n], not {list(P.shape)}")
         b = self.batch
         self._gen += 1
         b.set_reward_price(P.contiguous())
@@ -434,6 +488,8 @@ class VectorAggregator:
         if rb is None:
             cls, kw = self._batch_args
             rb = cls(self.homes, None, None, None, 0, (0.0,), groups=C * self.E, **kw)
+            if self.n_classes > 1:
+                rb.set_price_classes(self.price_class_host, self.n_classes)       # the same map
             self._sweep_batches[C] = rb
         for k in ("oat", "ghi", "tou", "start_index"):           # the live batch's environment (the same tensors)
             if hasattr(self.batch, k):
@@ -463,15 +519,23 @@ class VectorAggregator:
         if K < 1:
             raise ValueError(f"sweep takes steps >= 1, not {steps!r}")
         P = L.device_f64(prices, self.device)
-        if P.dim() == 2:
-            P = P.unsqueeze(-1)
-        if P.dim() != 3 or P.shape[0] != self.E or P.shape[1] < 1:
-            raise ValueError(f"sweep takes prices [{self.E}][C] or [{self.E}][C][n], not {list(P.shape)}")
+        nc = self.n_classes
+        if nc > 1:
+            if P.dim() == 3:
+                P = P.unsqueeze(-1)                              # class scalars
+            if P.dim() != 4 or P.shape[0] != self.E or P.shape[1] < 1 or P.shape[2] != nc:
+                raise ValueError(f"sweep takes class prices [{self.E}][C][{nc}] or [{self.E}][C][{nc}][n], not "
+                                 f"{list(P.shape)}")
+        else:
+            if P.dim() == 2:
+                P = P.unsqueeze(-1)
+            if P.dim() != 3 or P.shape[0] != self.E or P.shape[1] < 1:
+                raise ValueError(f"sweep takes prices [{self.E}][C] or [{self.E}][C][n], not {list(P.shape)}")
         C = int(P.shape[1])
-        Pc = P.permute(1, 0, 2).contiguous()                     # copy-major: [C][E][n]
+        Pc = P.transpose(0, 1).contiguous()                      # copy-major: [C][E][n] ([C][E][P][n] with classes)
         self._hold = None
         rb = self._sweep_batch(C)
-        rb.set_reward_price(Pc.view(C * self.E, -1))
+        rb.set_reward_price(Pc.view(C * self.E, nc, -1) if nc > 1 else Pc.view(C * self.E, -1))
         rb.replicate_from(self.batch)
         on = self.active()
         eff = torch.where(on, self.clocks, torch.full_like(self.clocks, -1))
@@ -531,7 +595,7 @@ class VectorAggregator:
         C, K = int(S.shape[1]), int(S.shape[2])
         last = getattr(self, "_paths", None)
         sums = last[1] if last is not None and last[0] is paths else S.permute(2, 1, 0, 3).reshape(K, C * E, 3).contiguous()
-        P = L.device_f64(prices, dev).reshape(E, C, -1).permute(1, 0, 2).reshape(C * E, -1).contiguous()
+        P = self._tie_rows(prices, C).contiguous()
         w = L.device_f64(weights, dev).reshape(-1).contiguous()
         if w.numel() != K:
             raise ValueError(f"select_paths takes {K} weights, not {w.numel()}")
@@ -555,8 +619,24 @@ class VectorAggregator:
         if S.dim() != 3 or S.shape[0] != self.E or S.shape[2] != 3:
             raise ValueError(f"select takes sums [{self.E}][C][3], not {list(S.shape)}")
         C = int(S.shape[1])
-        P = P.reshape(self.E, C, -1).permute(1, 0, 2).reshape(C * self.E, -1)
-        return self.batch.select_groups(S.permute(1, 0, 2).reshape(C * self.E, 3), setpoints, P)
+        return self.batch.select_groups(S.permute(1, 0, 2).reshape(C * self.E, 3), setpoints, self._tie_rows(P, C))
+
+    def tie_key(self, prices, C):
+        """The tie rule's key of every candidate, copy-major [C * E][1]: the sum over the classes, ascending, of
+        |first entry of the class's price row|, added left to right by elementwise ops (no host synchronisation).
+        One class: |first entry| -- what the select kernels themselves take of a price row."""
+        Q = L.device_f64(prices, self.device).reshape(self.E, C, self.n_classes, -1)[..., 0]
+        key = Q[..., 0].abs()
+        for c in range(1, self.n_classes):
+            key = key + Q[..., c].abs()
+        return key.t().reshape(C * self.E, 1)
+
+    def _tie_rows(self, prices, C):
+        """The price rows the select kernels read for their tie rule, copy-major [C * E][n]: without classes the
+        candidates' own rows, with classes `tie_key` (the kernels take |row[0]|, and the key is not negative)."""
+        if self.n_classes > 1:
+            return self.tie_key(prices, C)
+        return L.device_f64(prices, self.device).reshape(self.E, C, -1).permute(1, 0, 2).reshape(C * self.E, -1)
 
     def commit(self, choice):
         """Play, per episode, candidate choice[e] of the held sweep (`choice`: a device int tensor [E]): its
@@ -637,11 +717,14 @@ class VectorAggregator:
         self.batch.env_reset(st, m.contiguous())
 
     # ------------------------------------------------------------------ plan observations
-    def plan(self, keys, rows=(), out=None):
+    def plan(self, keys, rows=(), out=None, classes=False):
         """Every episode's planned curves, from the state its last step left (`MPCBatch.plan_groups`): device
         tensors (curve [E][nk][H], count [E][nk][H], stats [E][nr][4]).  A pure function of the hash arrays: a
         parked or finished episode's rows are those of its last step, a fresh one's empty (count 0).  No
-        synchronisation."""
+        synchronisation.  classes=True: per (episode, price class) -- curve and count [E][P][nk][H], stats
+        [E][P][nr][4] (`MPCBatch.plan_groups(classes=True)`, dragg_mpc_plan_classes)."""
+        if classes:
+            return self.batch.plan_groups(keys, rows, out=out, classes=True)
         return self.batch.plan_groups(keys, rows, out=out)
 
     # ------------------------------------------------------------------ rows for the host

@@ -539,6 +539,42 @@ typedef struct dragg_mpc_plan {
 int dragg_mpc_plan_groups(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash, const dragg_mpc_plan* plan,
                           void* stream);
 
+/* Price classes (since v10, additive): a reward price per class of homes in one community.  A class is an
+   integer 0 .. P - 1 per BASE home; the map belongs to the community and is shared by every group (episode,
+   sweep replica) of a grouped batch.  State has no class: dragg_mpc_replicate, dragg_mpc_adopt, the sums and the
+   environment entries are unchanged. */
+#define DRAGG_CLASS_MAX 64
+typedef struct dragg_mpc_classes {
+    int32_t n_classes;            /* P, 1 .. DRAGG_CLASS_MAX                                              */
+    const int32_t* price_class;   /* device [Nb], by base home (Nb = n_homes / max(n_groups, 1)); may be  */
+                                  /* NULL when P == 1                                                     */
+} dragg_mpc_classes;
+
+/* dragg_mpc_step_episodes with problem.reward_price read as [G][P][n_rp]: home r of group g = r / Nb reads row
+   g * P + price_class[r % Nb]; everything else about the step is dragg_mpc_step_episodes'.  Homes do not
+   interact within a step, so the columns of group g's class-c homes equal, bit for bit, those of the plain step
+   of group g under row (g, c) alone.  classes == NULL or n_classes == 1: the call IS dragg_mpc_step_episodes
+   (the same launches, the same bits; reward_price [G][n_rp]).  A class value outside 0 .. P - 1 is clamped into
+   that range by the kernel (the lookup is a scalar load per block: a block is one home): device data cannot make
+   it read past the price rows.  dragg_mpc_workspace_bytes is unchanged.  DRAGG_E_ARG: n_classes outside
+   1 .. DRAGG_CLASS_MAX, a NULL price_class with n_classes > 1, and wherever dragg_mpc_step_episodes returns it. */
+int dragg_mpc_step_classes(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob,
+                           const dragg_mpc_episodes* ep, const dragg_mpc_classes* classes, dragg_mpc_hash* hash,
+                           dragg_mpc_out* out, int32_t timestep, const double* noise, void* stream);
+
+/* dragg_mpc_plan_groups per (group, class): plan.curve and plan.count are [G][P][nk][H], plan.stats is
+   [G][P][nr][4].  Contract: class c's rows of group g equal dragg_mpc_plan_groups' rows of group g bit for bit
+   when the homes of g that are not in class c are absent -- every vals row of theirs (the solve counter
+   included) and every fc entry NaN.  The summation order is therefore dragg_mpc_plan_groups': the 16 ways run
+   over the GROUP's home positions i = w, w + 16, ... (not over the class's members), then the balanced tree; a
+   home of another class adds nothing and is not counted.  An empty class gets the empty result: sum +0.0, count
+   0, min +inf, max -inf.  A class value outside 0 .. P - 1 counts as clamped into it, as in the step.
+   classes == NULL or n_classes == 1: dragg_mpc_plan_groups' output ([G][...]).  One kernel, a grid plane per
+   class; vector stores, no atomics, no block reads what another writes.  DRAGG_E_ARG: dragg_mpc_plan_groups'
+   cases and the class ones of dragg_mpc_step_classes. */
+int dragg_mpc_plan_classes(const dragg_mpc_dims* dims, const dragg_mpc_hash* hash,
+                           const dragg_mpc_classes* classes, const dragg_mpc_plan* plan, void* stream);
+
 /* Lag mode (since v8): run_rbo_mpc's timestep loop (aggregator.py:757-778) has no feedback between
    homes, so a home whose chain needs the slow exact step-function DP need not hold up the others.
    A step is split into two passes the caller puts on two streams:

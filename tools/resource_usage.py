@@ -18,10 +18,11 @@ for line in err.splitlines():
         cur = m.group(1)
         rows[cur] = {}
         continue
-    m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs): (\d+)", line)
+    m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs|LDS Size \[bytes/block\]): (\d+)", line)
     if m and cur:
         rows[cur][m.group(1).split()[0]] = int(m.group(2))
 for k, v in rows.items():
     if "kernel" in k:
         name = re.sub(r"_ZN12_GLOBAL__N_1\d+", "", k)
-        print(f"{name[:60]:60s} VGPR {v.get('VGPRs')} AGPR {v.get('AGPRs')} scratch {v.get('ScratchSize')} occ {v.get('Occupancy')}")
+        print(f"{name:60s} VGPR {v.get('VGPRs')} AGPR {v.get('AGPRs')} scratch {v.get('ScratchSize')} "
+              f"LDS {v.get('LDS')} occ {v.get('Occupancy')}")
