@@ -12,6 +12,8 @@ Contents
                     reference's own variable / row order, solve, result extraction,
                     infeasibility fallback), solved with scipy HiGHS as the stand-in
                     for GLPK_MI (cvxpy/cvxopt/GLPK are absent from this image).
+`oracle.battery`    the battery LP of one solve alone (sparse, HiGHS at 1e-10, dual simplex
+                    or interior point): the checker of the GPU's piecewise-linear battery DP.
 `oracle.community`  restatement of the aggregator's per-timestep loop
                     (`aggregator.py:711-778`: dispatch, collect_data sums).
 

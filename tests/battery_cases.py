@@ -1,0 +1,194 @@
+"""Hard battery and PV cases for the default path's battery LP (`battery_lp`) and PV rule (`pv_curt`).
+
+One deterministic generator, shared by tests/test_oracle_battery.py (CPU: the reference and the
+generator's own conditions) and tests/test_gpu_battery.py (the kernel against the reference).  A
+plain helper module: no fixtures, no pytest hooks.
+
+A batch is one MPCBatch (the hems settings are batch-wide): the cross of 9 price families and 8
+battery families, 72 homes, half battery_only and half pv_battery, plus 4 homes with a 12-32 C
+comfort band (the family of test_wide_band_rl_price_second_launch_exact).  The thermal side is the
+same benign home in every case -- T0 and Tw0 mid-band, the outdoor air at T0, no water draws,
+summer -- so the battery is always reached.  Inputs go through MPCBatch.solve_explicit; no
+environment is needed.
+"""
+import functools
+from dataclasses import dataclass
+
+import numpy as np
+
+from oracle import mpc as M
+
+# (H, dt, discount): 31 / 32 / 33 straddle a 64-entry segment list (2H + 1 entries), 95 / 96 the
+# kernel's compact LDS layout; discount 1 with a constant price makes psi's slopes tie exactly
+# with the segments already in the list
+BATCHES = [(1, 1, 0.92), (2, 1, 0.92), (31, 1, 0.92), (32, 4, 0.92), (32, 4, 1.0), (33, 1, 0.92),
+           (48, 4, 0.92), (95, 5, 0.92), (95, 5, 1.0), (96, 4, 0.92)]
+
+PRICE_FAMILIES = ["positive", "negative", "alternating", "const_pos", "const_neg", "zero", "signed_zeros",
+                  "tiny_huge", "normal"]
+UNIFORM_SIGN = ("positive", "negative", "const_pos", "const_neg")
+BATTERY_FAMILIES = ["typical", "eta_one", "narrow", "point_box", "huge", "rate_zero", "at_emin", "at_emax"]
+E0_CHOICES = ["mid", "emin", "emax", "below_reachable", "above_reachable", "below_infeasible", "above_infeasible"]
+WIDE = "wide_band"
+
+T_BAND, T_WIDE = (19.0, 21.5), (12.0, 32.0)
+TW_BAND = (41.0, 52.0)
+OAT = 20.25                       # = T0 of the narrow band: the air stays put at zero duty
+P_MAG = 0.1
+# generator-typical battery ranges (dragg_amd.community.CONFIG_RANGES["battery"])
+B_RANGE = dict(max_rate=(3, 5), capacity=(9.0, 13.5), lower=(0.01, 0.15), upper=(0.85, 0.99), ch_eff=(0.85, 0.95),
+               disch_eff=(0.97, 0.99))
+
+
+@dataclass
+class Case:
+    name: str
+    price_family: str
+    battery_family: str
+    e0_choice: str
+    home: dict
+    hc: object                    # oracle.mpc.HomeConst
+    E0: float
+    T0: float
+    price: np.ndarray             # [H]
+    ghi: np.ndarray               # [H + 1]
+
+    def step_input(self):
+        H = self.hc.H
+        return M.StepInput(t=0, T0=self.T0, Tw0=0.5 * (TW_BAND[0] + TW_BAND[1]), E0=self.E0, oat=np.full(H + 1, OAT),
+                           ghi=self.ghi, price=self.price, draw=np.zeros(H + 1), winter=False)
+
+
+def batch_id(batch):
+    H, dt, disc = batch
+    return f"H{H}_dt{dt}_g{disc}"
+
+
+def _home(name, ty, batch, band, batt):
+    H, dt, disc = batch
+    assert H % dt == 0
+    h = {"name": name, "type": ty,
+         "hvac": {"r": 8.0, "c": 5.0, "p_c": 3.5, "p_h": 3.5, "temp_in_min": band[0], "temp_in_max": band[1],
+                  "temp_in_sp": 0.5 * (band[0] + band[1]), "temp_in_init": 0.5 * (band[0] + band[1])},
+         "wh": {"r": 22.0, "p": 2.5, "temp_wh_min": TW_BAND[0], "temp_wh_max": TW_BAND[1],
+                "temp_wh_sp": 0.5 * (TW_BAND[0] + TW_BAND[1]), "temp_wh_init": 0.5 * (TW_BAND[0] + TW_BAND[1]),
+                "tank_size": 250.0, "draw_sizes": [0.0] * 48},
+         "hems": {"horizon": H // dt, "hourly_agg_steps": dt, "sub_subhourly_steps": 6, "solver": "MI355X",
+                  "discount_factor": disc},
+         "battery": batt}
+    if "pv" in ty:
+        h["pv"] = {"area": 26.0, "eff": 0.18}
+    return h
+
+
+def _battery(fam, rng):
+    u = lambda k: float(rng.uniform(*B_RANGE[k]))  # noqa: E731
+    b = {"max_rate": u("max_rate"), "capacity": u("capacity"), "capacity_lower": u("lower"),
+         "capacity_upper": u("upper"), "ch_eff": u("ch_eff"), "disch_eff": u("disch_eff"), "e_batt_init": 0.5}
+    if fam == "eta_one":
+        b["ch_eff"] = b["disch_eff"] = 1.0
+    elif fam == "narrow":
+        b["capacity"] = 0.5                 # the box is narrower than one stage's charge
+    elif fam == "point_box":
+        b["capacity_lower"] = b["capacity_upper"] = 0.5
+    elif fam == "huge":
+        b["capacity"], b["max_rate"] = 1e4, 0.5     # never clipped: the list reaches 2H + 1 entries
+    elif fam == "rate_zero":
+        b["max_rate"] = 0.0
+    return b
+
+
+def _price(fam, H, rng):
+    mag = rng.uniform(0.05, 0.15, H)
+    if fam == "positive":
+        return mag
+    if fam == "negative":
+        return -mag
+    if fam == "alternating":
+        return mag * np.where(np.arange(H) % 2 == 0, 1.0, -1.0) * (1.0 if rng.integers(2) else -1.0)
+    if fam == "const_pos":
+        return np.full(H, P_MAG)
+    if fam == "const_neg":
+        return np.full(H, -P_MAG)
+    if fam == "zero":
+        return np.zeros(H)
+    if fam == "signed_zeros":
+        return rng.choice(np.array([0.0, -0.0, P_MAG, -P_MAG]), H)
+    if fam == "tiny_huge":
+        return rng.choice(np.array([1e-12, -1e-12, 1e3, -1e3]), H)
+    if fam == "normal":
+        return rng.normal(0.0, P_MAG, H)
+    raise ValueError(fam)
+
+
+def _e0(choice, b, dt):
+    """E0 of a choice: on the box, outside it by half a stage's reach, or two stages and 0.1 kWh
+    past it -- never within a quarter of a stage's reach of the limit between feasible and not,
+    unless exactly on Emin or Emax, so no solver tolerance decides a status."""
+    a, c, r = b["eta_c"] / dt, (1.0 / b["eta_d"]) / dt, b["rate"]
+    return {"mid": 0.5 * (b["Emin"] + b["Emax"]), "emin": b["Emin"], "emax": b["Emax"],
+            "below_reachable": b["Emin"] - 0.5 * a * r, "above_reachable": b["Emax"] + 0.5 * c * r,
+            "below_infeasible": b["Emin"] - 2 * a * r - 0.1, "above_infeasible": b["Emax"] + 2 * c * r + 0.1}[choice]
+
+
+@functools.lru_cache(maxsize=None)
+def cases(batch):
+    """The 76 cases of a batch, in the order of the MPCBatch's homes."""
+    H, dt, disc = batch
+    out = []
+    for pi, pf in enumerate(PRICE_FAMILIES):
+        for bi, bf in enumerate(BATTERY_FAMILIES):
+            rng = np.random.default_rng([H, dt, int(round(disc * 100)), pi, bi])
+            ty = "pv_battery" if (pi + bi) % 2 == 0 else "battery_only"
+            home = _home(f"{pf}-{bf}", ty, batch, T_BAND, _battery(bf, rng))
+            hc = M.home_const(home)
+            if bf == "at_emin":
+                choice = "emin"
+            elif bf == "at_emax":
+                choice = "emax"
+            elif bf == "huge" and pf in ("alternating", "normal"):
+                choice = "mid"                                  # the cases the list-length check rests on
+            else:
+                choice = E0_CHOICES[(pi + 2 * bi) % len(E0_CHOICES)]
+            price = _price(pf, H, rng)
+            ghi = rng.choice(np.array([0.0, 1.0]), H + 1) * rng.uniform(50.0, 900.0, H + 1)
+            if pf == "signed_zeros" and H >= 8:
+                # every (price sign, ghi zero or not) pair at least once per home
+                at = rng.permutation(H)[:8]
+                price[at] = np.repeat(np.array([0.0, -0.0, P_MAG, -P_MAG]), 2)
+                ghi[at] = np.tile(np.array([0.0, 400.0]), 4)
+            out.append(Case(home["name"], pf, bf, choice, home, hc, _e0(choice, hc.batt, dt), 0.5 * sum(T_BAND),
+                            price, ghi))
+    for j in range(4):
+        rng = np.random.default_rng([H, dt, int(round(disc * 100)), 99, j])
+        ty = "pv_battery" if j % 2 == 0 else "battery_only"
+        home = _home(f"{WIDE}-{j}", ty, batch, T_WIDE, _battery("typical", rng))
+        hc = M.home_const(home)
+        price = 0.08 + 0.03 * np.cos((np.arange(H) + j) / 3.0)     # stage-varying: the hot launch defers it
+        ghi = rng.choice(np.array([0.0, 1.0]), H + 1) * rng.uniform(50.0, 900.0, H + 1)
+        out.append(Case(home["name"], WIDE, "typical", "mid", home, hc, _e0("mid", hc.batt, dt), 0.5 * sum(T_WIDE),
+                        price, ghi))
+    return tuple(out)
+
+
+def explicit_inputs(cs):
+    """The [N] / [H + 1][N] arrays of MPCBatch.solve_explicit for the cases `cs`."""
+    n, H = len(cs), cs[0].hc.H
+    return dict(t=np.zeros(n, np.int32), T0=np.array([c.T0 for c in cs]),
+                Tw0=np.full(n, 0.5 * (TW_BAND[0] + TW_BAND[1])), E0=np.array([c.E0 for c in cs]),
+                counter=np.zeros(n, np.int32), winter=np.zeros(n, np.int32), draw=np.zeros((H + 1, n)),
+                oat=np.full((H + 1, n), OAT), ghi=np.array([c.ghi for c in cs]).T,
+                price=np.array([c.price for c in cs]).T)
+
+
+@functools.lru_cache(maxsize=None)
+def reference(batch, method="simplex"):
+    """oracle.battery.battery_lp of every case of a batch (computed once per process)."""
+    from oracle import battery as B
+    return tuple(B.battery_lp(c.hc, c.E0, c.price, method=method) for c in cases(batch))
+
+
+def moving_stages(c, x):
+    """The stages at which the trajectory `x` of case `c` changes the state of charge."""
+    E = np.r_[c.E0, x.E]
+    return int(np.sum(np.diff(E) != 0.0))
