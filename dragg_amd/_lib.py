@@ -142,6 +142,31 @@ def price_class_map(classes, n_homes, n_classes=None):
     return c.astype(np.int32), P
 
 
+# electric vehicles (dragg_ev_param, dragg_ev_key, dragg_ev_val, dragg_ev_status)
+EV_PARAMS = ["CAP", "EMIN", "EMAX", "RATE", "ETAC", "ETAD", "EINIT", "V2G", "DEPART", "RETURN", "TRIP", "EREQ"]
+NEVP = len(EV_PARAMS)
+EVP = {k: i for i, k in enumerate(EV_PARAMS)}
+EV_KEYS = ["p_ev_ch", "p_ev_disch", "e_ev_opt", "cost_ev"]
+NEVK = len(EV_KEYS)
+EV_VAL_KEYS = EV_KEYS + ["forecast_p_ev"]
+NEVV = len(EV_VAL_KEYS)
+EVK = {k: i for i, k in enumerate(EV_VAL_KEYS)}
+EV_OPTIMAL, EV_INFEASIBLE = 0, 1
+EV_WAVES = 4                   # DRAGG_EV_WAVES: vehicles per workgroup
+
+
+class Ev(ctypes.Structure):
+    """dragg_mpc_ev: a fleet's parameter rows, state (vals [NEVV][M], fc [M][NEVK][H]), status and objective."""
+    _fields_ = [("params", c_dp), ("vals", c_dp), ("fc", c_dp), ("status", c_dp), ("obj", c_dp),
+                ("day_offset", ctypes.c_int32), ("n_vehicles", ctypes.c_int32)]
+
+
+class EvExplicit(ctypes.Structure):
+    """dragg_mpc_ev_explicit: per-stage inputs [H][M] (row k of lo / hi: the box of E_{k+1}) and E0 [M]."""
+    _fields_ = [("price", c_dp), ("rate_ch", c_dp), ("rate_dis", c_dp), ("drain", c_dp), ("lo", c_dp), ("hi", c_dp),
+                ("E0", c_dp)]
+
+
 PLAN_WAYS = 16                 # DRAGG_PLAN_WAYS: the partial sums of a plan entry (part of its summation order)
 # the forecast keys a plan curve can hold (dragg_fc_key, bit k of dragg_mpc_plan.fc_keys) and the vals rows a plan
 # statistic can hold (dragg_val, bit r of val_rows), by their short names
@@ -231,7 +256,8 @@ EXPORTS = ["dragg_mpc_abi_version", "dragg_mpc_strerror", "dragg_mpc_lds_bytes",
            "dragg_mpc_replicate", "dragg_mpc_aggregate_groups", "dragg_mpc_step_episodes",
            "dragg_mpc_season_noise_episodes", "dragg_mpc_adopt", "dragg_mpc_select_groups", "dragg_mpc_env_file",
            "dragg_mpc_env_reset", "dragg_mpc_plan_groups", "dragg_mpc_select_paths", "dragg_mpc_step_classes",
-           "dragg_mpc_plan_classes"]
+           "dragg_mpc_plan_classes", "dragg_mpc_ev_lds_bytes", "dragg_mpc_ev_solve_explicit", "dragg_mpc_ev_step",
+           "dragg_mpc_ev_aggregate"]
 
 _LIB = None
 
@@ -310,6 +336,11 @@ def load(path=LIB_PATH):
                                            ctypes.c_int32, c_dp, c_dp]
     lib.dragg_mpc_plan_classes.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Hash), ctypes.POINTER(Classes),
                                            ctypes.POINTER(Plan), c_dp]
+    lib.dragg_mpc_ev_lds_bytes.argtypes = [ctypes.POINTER(Dims)]
+    lib.dragg_mpc_ev_solve_explicit.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ev), ctypes.POINTER(EvExplicit), c_dp]
+    lib.dragg_mpc_ev_step.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Problem), ctypes.POINTER(Ev), ctypes.c_int32,
+                                      c_dp]
+    lib.dragg_mpc_ev_aggregate.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ev), c_dp, c_dp]
     if lib.dragg_mpc_abi_version() != ABI_VERSION:
         raise DraggError("ABI version mismatch between dragg_amd and libdragg_mi355x.so")
     if not os.environ.get("DRAGG_LIB"):

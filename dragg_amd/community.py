@@ -91,12 +91,46 @@ def hourly_water_draws(n_homes, hours, rng, sizes):
     return np.clip(vol, 0, sizes[:, None])
 
 
+# electric vehicles (this project's own model): ranges of a `[home.ev]` config section;
+# depart_hour / return_hour are hours of day, drawn in whole steps
+EV_RANGES = dict(capacity=(40.0, 80.0), capacity_lower=(0.05, 0.15), capacity_upper=(0.85, 0.95), max_rate=(6.0, 11.0),
+                 ch_eff=(0.88, 0.95), disch_eff=(0.90, 0.97), e_ev_init=(0.4, 0.8), depart_hour=(6.0, 9.0),
+                 return_hour=(16.0, 19.0), trip_kwh=(5.0, 15.0), depart_soc=(0.5, 0.8), v2g_share=0.5)
+EV_SEED_TAG = 0xE7                      # the vehicles' generator is the homes' seed with this tag: a stream of its own
+
+
+def ev_sections(n, share, dt, seed, ranges=None):
+    """The "ev" sections of a community of n homes: {home index: section} for round(n * share) homes, spread
+    evenly over the list (every type and every strided shard gets its part), drawn from a generator of their own."""
+    R = dict(EV_RANGES, **{k: v for k, v in (ranges or {}).items() if k in EV_RANGES})
+    if not 0.0 <= float(share) <= 1.0:
+        raise ValueError(f"the share of homes with a vehicle must lie in 0..1, not {share!r}")
+    m = int(round(n * float(share)))
+    if m <= 0:
+        return {}
+    rng = np.random.default_rng([int(seed), EV_SEED_TAG])
+    out = {}
+    for j in range(m):
+        u = lambda k: float(rng.uniform(*R[k]))  # noqa: E731
+        dep = int(round(u("depart_hour") * dt))
+        ret = int(round(u("return_hour") * dt))
+        dep = min(max(dep, 0), 24 * dt - 1)
+        ret = min(max(ret, dep + 1), 24 * dt)
+        out[(j * n) // m] = {"capacity": u("capacity"), "capacity_lower": u("capacity_lower"),
+                             "capacity_upper": u("capacity_upper"), "max_rate": u("max_rate"), "ch_eff": u("ch_eff"),
+                             "disch_eff": u("disch_eff"), "e_ev_init": u("e_ev_init"),
+                             "v2g": bool(rng.uniform() < float(R["v2g_share"])), "depart_step": dep, "return_step": ret,
+                             "trip_kwh": u("trip_kwh"), "depart_soc": u("depart_soc")}
+    return out
+
+
 def synthetic_homes(n, mix=(0.4, 0.2, 0.2, 0.2), seed=12, days=2, dt=4, horizon_hours=6,
-                    sub_steps=6, discount=0.92):
+                    sub_steps=6, discount=0.92, ev_share=0.0):
     """n home dicts; mix = fractions of (base, pv_only, battery_only, pv_battery).
 
     Listed in the reference's order: pv_battery, pv_only, battery_only, base
-    (aggregator.py:392-560)."""
+    (aggregator.py:392-560).  ev_share > 0: that share of the homes gets an "ev" section (`ev_sections`, drawn
+    after everything else from a generator of its own: ev_share = 0 returns the same homes value for value)."""
     rng = np.random.default_rng(seed)
     n_pv = int(round(n * mix[1]))
     n_b = int(round(n * mix[2]))
@@ -134,6 +168,8 @@ def synthetic_homes(n, mix=(0.4, 0.2, 0.2, 0.2), seed=12, days=2, dt=4, horizon_
         if "pv" in ty:
             h["pv"] = {"area": rng.uniform(*PV["area"]), "eff": rng.uniform(*PV["eff"])}
         homes.append(h)
+    for i, sec in ev_sections(n, ev_share, dt, seed).items():
+        homes[i]["ev"] = sec
     return homes
 
 

@@ -5517,6 +5517,314 @@ __global__ void noise_kernel(int N, int H, dragg_mpc_episodes ep, uint64_t seed,
 }
 
 // --------------------------------------------------------------------------------------
+// Electric vehicles (dragg_mpc_ev_*): the stage-varying storage LP
+//   min sum_k q_k (ch_k + dis_k),  E_{k+1} = E_k + a ch_k + b dis_k - drain_k,  0 <= ch_k <= rc_k,
+//   -rd_k <= dis_k <= 0,  lo_k <= E_{k+1} <= hi_k,  q_k = S gamma^k price_k.
+// battery_lp's recursion with per-stage arrays: psi_k from (rc_k, rd_k), the merged domain origin
+// x0 + x0psi_k + drain_k (V_k(E) = min_z psi_k(z) + V_{k+1}(E - z - drain_k)), the cut to stage k's own box;
+// recovery forward as there.  The expressions keep battery_lp's shapes, so that with rc = rd = r, drain = 0 and
+// a constant box the arithmetic is battery_lp's to the bit.  One wave per vehicle, EV_WAVES vehicles per
+// workgroup, each with its own slice of the dynamic LDS; the waves never meet (wave_sync only: a wave past the
+// last vehicle simply leaves).
+// --------------------------------------------------------------------------------------
+constexpr int EV_WAVES = DRAGG_EV_WAVES;
+constexpr int EV_NT = EV_WAVES * WAVE;
+constexpr int EV_ROWS = 13;
+__host__ __device__ inline int ev_lds_doubles(int H) { return 4 * seg_cap(H) + EV_ROWS * H; }
+
+struct EvLds {
+    double *sgS, *sgL;                      // segment lists [2][seg_cap]: slopes, lengths
+    double *pi, *q, *rc, *rd, *dr, *lo, *hi; // [H] price, cost row, rates, drain, the box of E_{k+1}
+    double *bx0, *bp1, *bp2;                // [H] recovery: merged origin, offsets of psi's segments
+    double *ch, *dis, *E;                   // [H] the trajectory (E[k] = E_{k+1})
+};
+struct EvCar {
+    int H, S, dt;
+    double gamma, etac, etad, Emax, cap, E0;
+};
+struct EvArgs {
+    dragg_mpc_dims d;
+    dragg_mpc_ev ev;
+    dragg_mpc_ev_explicit ex;
+    const double *tou, *reward_price;
+    int start_index, t, G;
+};
+
+DEV EvLds ev_carve(double* s, int H) {
+    const int cap = seg_cap(H);
+    EvLds L;
+    L.sgS = s; s += 2 * cap;
+    L.sgL = s; s += 2 * cap;
+    L.pi = s; s += H;  L.q = s; s += H;   L.rc = s; s += H;  L.rd = s; s += H;
+    L.dr = s; s += H;  L.lo = s; s += H;  L.hi = s; s += H;
+    L.bx0 = s; s += H; L.bp1 = s; s += H; L.bp2 = s; s += H;
+    L.ch = s; s += H;  L.dis = s; s += H; L.E = s;
+    return L;
+}
+
+// a product that is never contracted into a following add.  battery_lp's a r and b r are loop invariants, computed
+// before its loops, so no add of its loops fuses with them; here the rates change by stage and the products stand
+// next to those adds
+DEV double ev_mul(double x, double y) {
+#pragma clang fp contract(off)
+    return x * y;
+}
+DEV void ev_psi(double a, double b, double q, double rc, double rd, double* s1, double* l1, double* s2, double* l2) {
+    const double ar = ev_mul(a, rc), br = ev_mul(b, rd);
+    if (q >= 0.0) { *s1 = -q / a; *l1 = ar; *s2 = -q / b; *l2 = br; }   // charge | discharge
+    else          { *s1 = -q / b; *l1 = br; *s2 = -q / a; *l2 = ar; }   // full-charge edge first
+}
+
+DEV bool ev_lp(const EvCar& c, const EvLds& L, int lane) {
+    const int H = c.H;
+    const int cap = seg_cap(H);
+    const double a = c.etac / c.dt, b = (1.0 / c.etad) / c.dt;
+    double* S0 = L.sgS;  double* L0 = L.sgL;          // current list
+    double* S1 = L.sgS + cap; double* L1 = L.sgL + cap;
+    int n = 1;
+    double x0 = L.lo[H - 1];                          // V_H: free inside the last box, slope 0
+    const double hiH = L.hi[H - 1];
+    if (!(x0 <= hiH + TOL_P * (1 + fabs(hiH)))) return false;
+    if (lane == 0) { S0[0] = 0.0; L0[0] = fmax(0.0, hiH - x0); }
+    wave_sync();
+    bool feasible = true;
+    for (int k = H - 1; k >= 0; --k) {
+        const double r = L.rc[k], rd = L.rd[k];
+        const double x0psi = -ev_mul(a, r);
+        double s1, l1, s2, l2;
+        ev_psi(a, b, L.q[k], r, rd, &s1, &l1, &s2, &l2);
+        // ranks: psi's segments go after existing segments of equal slope
+        int c1 = 0, c2 = 0;
+        double p1 = 0.0, p2 = 0.0;
+        for (int i = lane; i < n; i += WAVE) {
+            const double si = S0[i], li = L0[i];
+            if (si <= s1) { ++c1; p1 += li; }
+            if (si <= s2) { ++c2; p2 += li; }
+        }
+        c1 = dpp_isum(c1); c2 = dpp_isum(c2);
+        p1 = dpp_sum(p1); p2 = dpp_sum(p2);
+        const int r1 = c1, r2 = c2 + 1;               // merged positions of psi's segments
+        p2 += l1;                                     // psi 1 precedes psi 2 (s1 <= s2)
+        for (int i = lane; i < n; i += WAVE) {
+            const double si = S0[i];
+            const int j = i + (s1 < si ? 1 : 0) + (s2 < si ? 1 : 0);
+            S1[j] = si; L1[j] = L0[i];
+        }
+        if (lane == 0) { S1[r1] = s1; L1[r1] = l1; S1[r2] = s2; L1[r2] = l2; }
+        const double X0M = x0 + x0psi + L.dr[k];      // E_k = E_{k+1} + z + drain_k
+        if (lane == 0) { L.bx0[k] = X0M; L.bp1[k] = p1; L.bp2[k] = p2; }
+        n += 2;
+        wave_sync();
+        double tot = 0.0;
+        for (int i = lane; i < n; i += WAVE) tot += L1[i];
+        tot = dpp_sum(tot);
+        if (k == 0) {                                 // E_0 is fixed: it must lie in the domain
+            const double p = c.E0 - X0M;
+            feasible = p >= -TOL_P * (1 + fabs(c.E0)) && p <= tot + TOL_P * (1 + fabs(c.E0));
+            break;
+        }
+        // cut the merged list to E_k's own box (k >= 1: row k - 1)
+        const double blo = L.lo[k - 1], bhi = L.hi[k - 1];
+        const double cl = fmax(0.0, blo - X0M), chi = fmin(tot, bhi - X0M);
+        if (!(cl <= chi + TOL_P * (1 + fabs(bhi)))) { feasible = false; break; }
+        // exclusive prefix of lengths in list order (lane-contiguous chunks)
+        const int per = (n + WAVE - 1) / WAVE;
+        const int i0 = lane * per, i1 = min(n, i0 + per);
+        double loc = 0.0;
+        for (int i = i0; i < i1; ++i) loc += L1[i];
+        const double inc = dpp_scan(loc, lane);
+        double pre = inc - loc;
+        int first = n, last = -1;
+        for (int i = i0; i < i1; ++i) {
+            const double st = pre, en = pre + L1[i];
+            const double ns = fmax(st, cl), ne = fmin(en, chi);
+            if (ne > ns) { first = min(first, i); last = max(last, i); }
+            L1[i] = fmax(0.0, ne - ns);
+            pre = en;
+        }
+        first = dpp_imin(first);
+        last = dpp_imax(last);
+        wave_sync();
+        const int nn = last >= first ? last - first + 1 : 0;
+        for (int i = lane; i < nn; i += WAVE) { S0[i] = S1[first + i]; L0[i] = L1[first + i]; }
+        if (nn == 0 && lane == 0) { S0[0] = 0.0; L0[0] = 0.0; }   // a single feasible point
+        n = nn == 0 ? 1 : nn;
+        x0 = X0M + cl;
+        wave_sync();
+    }
+    if (!feasible) return false;
+    if (lane == 0) {                                  // forward recovery of E, ch, dis
+        double E = c.E0;
+        for (int k = 0; k < H; ++k) {
+            const double r = L.rc[k], rd = L.rd[k], qk = L.q[k];
+            const double x0psi = -ev_mul(a, r);
+            double s1, l1, s2, l2;
+            ev_psi(a, b, qk, r, rd, &s1, &l1, &s2, &l2);
+            const double p = E - L.bx0[k];
+            const double z = x0psi + fmin(fmax(p - L.bp1[k], 0.0), l1) + fmin(fmax(p - L.bp2[k], 0.0), l2);
+            const double dlt = -z;                   // a ch_k + b dis_k
+            double chv, dis;
+            if (qk >= 0.0) {
+                if (dlt >= 0.0) { chv = fmin(dlt / a, r); dis = 0.0; }
+                else            { chv = 0.0; dis = fmax(dlt / b, -rd); }
+            } else {
+                chv = fmin(r, (dlt + ev_mul(b, rd)) / a);
+                dis = fmax(-rd, fmin(0.0, (dlt - a * chv) / b));
+            }
+            E = E + (c.etac * chv + dis / c.etad) / c.dt - L.dr[k];
+            L.ch[k] = chv;
+            L.dis[k] = dis;
+            L.E[k] = E;
+        }
+    }
+    wave_sync();
+    return true;
+}
+
+// the uncontrolled rule (no trajectory), one lane, ascending k; contraction off, so that the same operations in
+// the same order on the host give the same bits
+DEV void ev_fallback(const EvCar& c, const EvLds& L) {
+#pragma clang fp contract(off)
+    const double a = c.etac / c.dt;
+    double E = c.E0;
+    for (int k = 0; k < c.H; ++k) {
+        const double room = (c.Emax - E) / a;
+        const double chv = fmin(L.rc[k], fmax(0.0, room));
+        E = fmin(fmax((E + a * chv) - L.dr[k], 0.0), c.cap);
+        L.ch[k] = chv;
+        L.dis[k] = 0.0;
+        L.E[k] = E;
+    }
+}
+
+// sum_k q_k (ch_k + dis_k) in ascending k, no contraction (one lane)
+DEV double ev_objective(const EvLds& L, int H) {
+#pragma clang fp contract(off)
+    double s = 0.0;
+    for (int k = 0; k < H; ++k) s += L.q[k] * (L.ch[k] + L.dis[k]);
+    return s;
+}
+
+// STEP: the stage arrays from the vehicle's parameters, the clock and the price (dragg_mpc_ev_step); else the
+// explicit ones.  Everything after the prologue is one code path.
+template <bool STEP>
+__global__ __launch_bounds__(EV_NT) void ev_kernel(EvArgs a) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int wid = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+    const int M = a.ev.n_vehicles;
+    const int r = __builtin_amdgcn_readfirstlane((int)blockIdx.x * EV_WAVES + wid);
+    if (r >= M) return;
+    const int H = a.d.horizon;
+    const EvLds L = ev_carve(smem + (size_t)wid * ev_lds_doubles(H), H);
+    const double* P = a.ev.params;
+    EvCar c;
+    c.H = H; c.S = a.d.sub_steps; c.dt = a.d.dt; c.gamma = a.d.discount;
+    c.etac = P[(size_t)DRAGG_EVP_ETAC * M + r];
+    c.etad = P[(size_t)DRAGG_EVP_ETAD * M + r];
+    c.Emax = P[(size_t)DRAGG_EVP_EMAX * M + r];
+    c.cap = P[(size_t)DRAGG_EVP_CAP * M + r];
+    if (STEP) {
+        const double Emin = P[(size_t)DRAGG_EVP_EMIN * M + r], rate = P[(size_t)DRAGG_EVP_RATE * M + r];
+        const bool v2g = P[(size_t)DRAGG_EVP_V2G * M + r] != 0.0;
+        const int dep = (int)P[(size_t)DRAGG_EVP_DEPART * M + r], ret = (int)P[(size_t)DRAGG_EVP_RETURN * M + r];
+        const bool trips = ret > dep;                      // (pack_evs refuses anything else)
+        const double drain = trips ? P[(size_t)DRAGG_EVP_TRIP * M + r] / (double)(ret - dep) : 0.0;
+        const double lo_dep = fmax(Emin, P[(size_t)DRAGG_EVP_EREQ * M + r]);
+        const int D = 24 * c.dt;
+        const int c0 = (a.ev.day_offset + a.t) % D;
+        const int s0 = a.start_index + a.t;
+        const int n_rp = a.d.n_rp;
+        const double* rpl = a.reward_price + (size_t)((unsigned)r / ((unsigned)M / (unsigned)a.G)) * n_rp;
+        for (int k = lane; k < H; k += WAVE) {
+            const int sk = (c0 + k) % D, sn = (c0 + k + 1) % D;
+            const bool away = trips && dep <= sk && sk < ret;
+            const double rc = away ? 0.0 : rate;
+            const double rp = rpl[n_rp == 1 ? 0 : (k < n_rp ? k : n_rp - 1)];
+            L.pi[k] = rp + a.tou[s0 + k];
+            L.rc[k] = rc;
+            L.rd[k] = v2g ? rc : 0.0;
+            L.dr[k] = away ? drain : 0.0;
+            L.lo[k] = trips && sn == dep ? lo_dep : Emin;
+            L.hi[k] = c.Emax;
+        }
+        c.E0 = a.t == 0 ? P[(size_t)DRAGG_EVP_EINIT * M + r] : a.ev.vals[(size_t)DRAGG_EVK_E * M + r];
+    } else {
+        for (int k = lane; k < H; k += WAVE) {
+            const size_t i = (size_t)k * M + r;
+            L.pi[k] = a.ex.price[i];
+            L.rc[k] = a.ex.rate_ch[i];
+            L.rd[k] = a.ex.rate_dis[i];
+            L.dr[k] = a.ex.drain[i];
+            L.lo[k] = a.ex.lo[i];
+            L.hi[k] = a.ex.hi[i];
+        }
+        c.E0 = a.ex.E0[r];
+    }
+    wave_sync();
+    // the home kernel's battery cost row, expression for expression
+    for (int k = lane; k < H; k += WAVE) L.q[k] = pow(c.gamma, (double)k) * L.pi[k] * c.S;
+    wave_sync();
+    const bool ok = ev_lp(c, L, lane);
+    double obj = __builtin_nan("");
+    if (lane == 0) {
+        if (ok) obj = ev_objective(L, H);
+        else ev_fallback(c, L);
+    }
+    wave_sync();
+    double* fc = a.ev.fc + (size_t)r * DRAGG_NEVK * H;
+    for (int k = lane; k < H; k += WAVE) {
+        const double chv = L.ch[k], dis = L.dis[k];
+        fc[DRAGG_EVK_P_CH * H + k] = chv;
+        fc[DRAGG_EVK_P_DISCH * H + k] = dis;
+        fc[DRAGG_EVK_E * H + k] = L.E[k];
+        fc[DRAGG_EVK_COST * H + k] = L.pi[k] * (c.S * (chv + dis));
+    }
+    if (lane == 0) {
+        double* v = a.ev.vals;
+        const double ch0 = L.ch[0], dis0 = L.dis[0];
+        v[(size_t)DRAGG_EVK_P_CH * M + r] = ch0;
+        v[(size_t)DRAGG_EVK_P_DISCH * M + r] = dis0;
+        v[(size_t)DRAGG_EVK_E * M + r] = L.E[0];
+        v[(size_t)DRAGG_EVK_COST * M + r] = L.pi[0] * (c.S * (ch0 + dis0));
+        v[(size_t)DRAGG_EVV_FORECAST_P * M + r] = H > 1 ? L.ch[1] + L.dis[1] : 0.0;
+        a.ev.status[r] = ok ? DRAGG_EV_OPTIMAL : DRAGG_EV_INFEASIBLE;
+        a.ev.obj[r] = obj;
+    }
+}
+
+// dragg_mpc_ev_aggregate: block g sums group g's Mb vehicles (the header's order)
+__global__ __launch_bounds__(AGG_NT) void ev_aggregate_kernel(const double* vals, int M, int Mb, double* out) {
+#pragma clang fp contract(off)
+    __shared__ double red[3][AGG_NT / WAVE];
+    const size_t off = (size_t)blockIdx.x * Mb;
+    const double* pc = vals + (size_t)DRAGG_EVK_P_CH * M + off;
+    const double* pd = vals + (size_t)DRAGG_EVK_P_DISCH * M + off;
+    const double* pf = vals + (size_t)DRAGG_EVV_FORECAST_P * M + off;
+    const double* pk = vals + (size_t)DRAGG_EVK_COST * M + off;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int i = threadIdx.x; i < Mb; i += AGG_NT) {
+        s0 += pc[i] + pd[i];
+        s1 += pf[i];
+        s2 += pk[i];
+    }
+    s0 = dpp_sum(s0); s1 = dpp_sum(s1); s2 = dpp_sum(s2);
+    const int w = threadIdx.x / WAVE;
+    if ((threadIdx.x & (WAVE - 1)) == 0) { red[0][w] = s0; red[1][w] = s1; red[2][w] = s2; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double t[AGG_NT / WAVE];
+#pragma unroll
+        for (int m = 0; m < AGG_NT / WAVE; ++m) t[m] = red[threadIdx.x][m];
+#pragma unroll
+        for (int width = AGG_NT / WAVE / 2; width >= 1; width /= 2)
+#pragma unroll
+            for (int m = 0; m < width; ++m) t[m] = t[2 * m] + t[2 * m + 1];
+        out[(size_t)blockIdx.x * 3 + threadIdx.x] = t[0];
+    }
+}
+
+// --------------------------------------------------------------------------------------
 // Host layer.  Sizes and check_dims; the knobs; one description per launch (struct Launch: kernel,
 // threads, LDS) run through `run`, which raises the kernel's LDS limit once per device; the launch
 // sequences (launch: the serial step, launch_lag: one pass of a lag-mode step, both ending in
@@ -5812,6 +6120,33 @@ int solve_args(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, const 
     a->step_work_cap = knobs().step_work_cap;
     a->narrow_lds = knobs().narrow_lds;
     return DRAGG_OK;
+}
+
+// the EV entries' shared check (check_dims first) and the kernel arguments' common part; the groups come back in *G
+size_t ev_block_lds(int H) { return (size_t)EV_WAVES * ev_lds_doubles(H) * sizeof(double); }
+int ev_args(const dragg_mpc_dims* dims, const dragg_mpc_ev* ev, EvArgs* a) {
+    const int rc = check_dims(dims);
+    if (rc) return rc;
+    if (ev_block_lds(dims->horizon) > (size_t)LDS_DYN_MAX) return DRAGG_E_HORIZON;
+    if (!ev || ev->n_vehicles < 0 || ev->day_offset < 0 || ev->day_offset >= 24 * dims->dt) return DRAGG_E_ARG;
+    const int G = max(dims->n_groups, 1);
+    if (ev->n_vehicles % G != 0) return DRAGG_E_ARG;
+    *a = EvArgs{};
+    a->d = *dims;
+    a->ev = *ev;
+    a->G = G;
+    return DRAGG_OK;
+}
+template <bool STEP>
+int ev_launch(const EvArgs& a, hipStream_t s) {
+    int dev;
+    if (int rc = current_device(&dev)) return rc;
+    const void* kern = reinterpret_cast<const void*>(&ev_kernel<STEP>);
+    if (!raise_lds_limit(dev, kern)) return DRAGG_E_LDS;
+    const int blocks = (a.ev.n_vehicles + EV_WAVES - 1) / EV_WAVES;
+    void* args[] = {const_cast<EvArgs*>(&a)};
+    (void)hipLaunchKernel(kern, dim3(blocks), dim3(EV_NT), args, ev_block_lds(a.d.horizon), s);
+    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
 }
 
 }  // namespace
@@ -6287,6 +6622,55 @@ int dragg_mpc_plan_classes(const dragg_mpc_dims* dims, const dragg_mpc_hash* has
     const int cls = classes_in_effect(classes);
     if (cls < 0) return DRAGG_E_ARG;
     return plan_launch(dims, hash, plan, cls ? classes->price_class : nullptr, cls ? classes->n_classes : 1, stream);
+}
+
+int dragg_mpc_ev_lds_bytes(const dragg_mpc_dims* dims) {
+    const int rc = check_dims(dims);
+    if (rc) return rc;
+    return ev_block_lds(dims->horizon) > (size_t)LDS_DYN_MAX ? DRAGG_E_HORIZON : (int)ev_block_lds(dims->horizon);
+}
+
+static bool ev_state_ok(const dragg_mpc_ev* ev) { return ev->params && ev->vals && ev->fc && ev->status && ev->obj; }
+
+int dragg_mpc_ev_solve_explicit(const dragg_mpc_dims* dims, const dragg_mpc_ev* ev, const dragg_mpc_ev_explicit* in,
+                                void* stream) {
+    EvArgs a;
+    const int rc = ev_args(dims, ev, &a);
+    if (rc) return rc;
+    if (!in || a.G > 1) return DRAGG_E_ARG;
+    if (ev->n_vehicles == 0) return DRAGG_OK;
+    if (!ev_state_ok(ev) || !in->price || !in->rate_ch || !in->rate_dis || !in->drain || !in->lo || !in->hi || !in->E0)
+        return DRAGG_E_ARG;
+    a.ex = *in;
+    return ev_launch<false>(a, (hipStream_t)stream);
+}
+
+int dragg_mpc_ev_step(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, const dragg_mpc_ev* ev,
+                      int32_t timestep, void* stream) {
+    EvArgs a;
+    const int rc = ev_args(dims, ev, &a);
+    if (rc) return rc;
+    if (!prob || timestep < 0) return DRAGG_E_ARG;
+    if (ev->n_vehicles == 0) return DRAGG_OK;
+    if (!ev_state_ok(ev) || !prob->tou || !prob->reward_price) return DRAGG_E_ARG;
+    if (dims->n_rp != 1 && dims->n_rp < dims->horizon) return DRAGG_E_ARG;
+    if (prob->start_index < 0 || (long long)prob->start_index + timestep + dims->horizon >= (long long)dims->n_env)
+        return DRAGG_E_ARG;
+    a.tou = prob->tou;
+    a.reward_price = prob->reward_price;
+    a.start_index = prob->start_index;
+    a.t = timestep;
+    return ev_launch<true>(a, (hipStream_t)stream);
+}
+
+int dragg_mpc_ev_aggregate(const dragg_mpc_dims* dims, const dragg_mpc_ev* ev, double* out, void* stream) {
+    EvArgs a;
+    const int rc = ev_args(dims, ev, &a);
+    if (rc) return rc;
+    if (!out || (ev->n_vehicles > 0 && !ev->vals)) return DRAGG_E_ARG;
+    hipLaunchKernelGGL(ev_aggregate_kernel, dim3(a.G), dim3(AGG_NT), 0, (hipStream_t)stream, ev->vals, ev->n_vehicles,
+                       ev->n_vehicles / a.G, out);
+    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
 }
 
 }  // extern "C"

@@ -123,6 +123,7 @@ class Aggregator:
         from .aggregator import DeviceAggregator
         self.checked, oat, ghi, tou = self._checked_community()
         self._hist_rows = 0                 # steps of the history already on rank 0 (_history)
+        fleet = self._fleet(tou)
         self.dev = DeviceAggregator(self.checked, oat, ghi, tou, self.start_hour_index,
                                     self.num_timesteps, reward_price=self.reward_price, int_mode=self.int_mode,
                                     seed=int(self.config["simulation"]["random_seed"]), rank=self.rank,
@@ -130,8 +131,52 @@ class Aggregator:
                                     # run_rbo_mpc: a home in its step-function DP does not hold up the
                                     # others (lag mode, DeviceAggregator); results are bit-identical
                                     overlap=getattr(self, "case", None) == "baseline",
+                                    **({"ev": fleet} if fleet is not None else {}),
                                     **({"batch_cls": self.batch_cls} if self.batch_cls else {}))
         return self.dev
+
+    def _fleet(self, tou):
+        """The optional `[home.ev]` config section (`share`, and any range of community.EV_RANGES): that share of
+        the checked homes gets a vehicle (community.ev_sections: a generator of its own, keyed by the run's seed)
+        and this rank's shard of them becomes an EVFleet beside the homes.  The home dicts themselves are not
+        touched: results.json and the all-homes file are what they are without the section.  None without it."""
+        cfg = self.config["home"].get("ev")
+        if not cfg or float(cfg.get("share", 0.0)) <= 0.0:
+            return None
+        from .community import ev_sections
+        from .ev import build_fleet
+        secs = ev_sections(len(self.checked), cfg["share"], self.dt, int(self.config["simulation"]["random_seed"]), cfg)
+        homes = [dict(h, ev=secs[i]) if i in secs else h for i, h in enumerate(self.checked)]
+        day_offset = (self.start_dt.hour * self.dt + self.start_dt.minute // self.dt_interval) % (24 * self.dt)
+        return build_fleet(homes, tou=tou, start_index=self.start_hour_index, reward_price=self.reward_price,
+                           day_offset=day_offset, rank=self.rank, world=self.world,
+                           **({"device": self.device} if self.device is not None else {}))
+
+    def write_ev_outputs(self):
+        """`ev.json` next to results.json: per vehicle its four series and its statuses, and the community's
+        p_grid_aggregate with the vehicles (agg_hist's loads).  With more than one rank each rank writes its own
+        vehicles (`ev-rank<r>-of-<w>.json`)."""
+        dev = self.dev
+        if dev is None or getattr(dev, "ev", None) is None:
+            return None
+        from . import _lib as L
+        dev.drain()
+        T = dev.timestep
+        hist = dev.ev_hist[:T].cpu().numpy()
+        status = dev.ev_status_hist[:T].cpu().numpy()
+        out = {"vehicles": {}}
+        for j, name in enumerate(dev.ev.names):
+            rec = {k: hist[:, L.EVK[k], j].tolist() for k in L.EV_KEYS}
+            rec["status"] = status[:, j].tolist()
+            out["vehicles"][name] = rec
+        out["Summary"] = {"p_grid_aggregate": dev.agg_hist[:T, 0].cpu().numpy().tolist()}
+        d = os.path.join(self.run_dir, self.case)
+        os.makedirs(d, exist_ok=True)
+        name = "ev.json" if self.world == 1 else f"ev-rank{self.rank}-of-{self.world}.json"
+        path = os.path.join(d, name)
+        with open(path, "w") as f:
+            json.dump(out, f)
+        return path
 
     def state_path(self):
         """This rank's device-state checkpoint, next to results.json (<run dir>/<case>/)."""
@@ -229,6 +274,9 @@ class Aggregator:
         from .vector import VectorAggregator
         if self.world > 1:
             raise ValueError("rl_vector runs on one rank: episodes are not sharded over ranks")
+        if float(((self.config.get("home") or {}).get("ev") or {}).get("share", 0.0)) > 0.0:
+            raise NotImplementedError("rl_vector: the vector environments do not take an EV fleet yet; this config's "
+                                      "[home.ev] section is served by run() and run_rl_agg only")
         if not hasattr(self, "start_hour_index"):
             self.flush()
         E = int(episodes)
@@ -430,6 +478,7 @@ class Aggregator:
                 self.write_outputs()
         self.dev.check_errors()
         self.check_solve_paths()
+        self.write_ev_outputs()
         return self.write_outputs()
 
     def _history(self):
@@ -529,6 +578,7 @@ class Aggregator:
             self.run_baseline(noise_fn, resume=resume, stop_after=stop_after)
             if stop_after is not None and self.timestep < self.num_timesteps:
                 return None
+            self.write_ev_outputs()
             return self.write_outputs()
         if sim.get("run_rl_agg"):
             if resume or stop_after is not None:

@@ -295,12 +295,15 @@ class HeldReplicas:
 class VectorAggregator:
     def __init__(self, homes, oat, ghi, tou, episodes, seeds, start_indices, num_timesteps, int_mode="round",
                  keep_history=True, device=None, batch_cls=MPCBatch, rank=0, world=1, price_classes=None,
-                 n_classes=None, **batch_kw):
+                 n_classes=None, ev=None, **batch_kw):
         """price_classes ("type", or an int sequence [Nb] with `n_classes` = P; default None: one price for the
         community): the community's price classes (`resolve_price_classes`, `MPCBatch.set_price_classes`), shared by
         every episode and every sweep replica.  With P > 1 an action is a price per class: `step` takes [E][P] or
         [E][P][n], `sweep` [E][C][P] or [E][C][P][n] -- a 2-D `step` tensor and a 3-D `sweep` tensor then mean class
         scalars, never price lists.  `n_classes`, `class_names` and `price_class_host` describe the map."""
+        if ev is not None:
+            raise NotImplementedError("the vector environments do not take an EV fleet yet: the vehicles follow one "
+                                      "shared clock and price (DeviceAggregator(ev=...)), not per-episode ones")
         if world > 1:
             raise ValueError("VectorAggregator runs on one rank: episodes are not sharded over ranks")
         E = int(episodes)

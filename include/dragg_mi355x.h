@@ -621,6 +621,102 @@ int dragg_mpc_aggregate_rows(const dragg_mpc_dims* dims, const double* rows, int
 int dragg_mpc_season_noise(const dragg_mpc_dims* dims, uint64_t seed, int32_t home_offset,
                            int32_t home_stride, int32_t timestep, double* noise_out, void* stream);
 
+/* Electric vehicles (since v10, additive): an exact stage-varying storage LP per vehicle, solved beside the homes.
+   The reference has no vehicle; the model is this project's.  A vehicle is one more
+   separable block of a home: with a = ch_eff / dt, b = 1 / (disch_eff dt) and q_k = S gamma^k price_k (the
+   expression of the home kernel's battery cost row),
+       minimise sum_k q_k (ch_k + dis_k),   E_{k+1} = E_k + a ch_k + b dis_k - drain_k,
+       0 <= ch_k <= rate_ch_k,   -rate_dis_k <= dis_k <= 0,   lo_k <= E_{k+1} <= hi_k        (k = 0 .. H - 1)
+   with E_0 fixed.  The cost-to-go is convex piecewise linear; it is carried backward as a sorted segment list
+   (the battery LP's recursion with per-stage rates, drift and box) and the optimum is recovered forward: exact,
+   no iteration.  One wave per vehicle.  Nothing here reads or writes a home's arrays, and no home entry reads
+   these.  M = n_vehicles vehicles; with dims.n_groups = G > 1 they are G consecutive replicas of M / G base
+   vehicles (M % G == 0), vehicle r in group r / (M / G).  dims.n_homes is only checked (the usual dims check),
+   never read: a fleet passes its own M there.  Episode clocks and price classes do not reach the vehicles. */
+enum dragg_ev_param {           /* rows of dragg_mpc_ev.params [DRAGG_NEVP][M] */
+    DRAGG_EVP_CAP = 0,          /* ev.capacity (kWh)                              */
+    DRAGG_EVP_EMIN,             /* ev.capacity_lower * capacity                   */
+    DRAGG_EVP_EMAX,             /* ev.capacity_upper * capacity                   */
+    DRAGG_EVP_RATE,             /* ev.max_rate (kW)                               */
+    DRAGG_EVP_ETAC, DRAGG_EVP_ETAD,
+    DRAGG_EVP_EINIT,            /* ev.e_ev_init * capacity                        */
+    DRAGG_EVP_V2G,              /* 1.0: may discharge to the home, 0.0: may not   */
+    DRAGG_EVP_DEPART,           /* step of day the vehicle leaves                 */
+    DRAGG_EVP_RETURN,           /* step of day it is back (depart < return)       */
+    DRAGG_EVP_TRIP,             /* ev.trip_kwh, drained evenly over the away steps */
+    DRAGG_EVP_EREQ,             /* ev.depart_soc * capacity                       */
+    DRAGG_NEVP
+};
+/* the vehicle's horizon rows fc[M][DRAGG_NEVK][H] (vehicle-contiguous, like dragg_mpc_hash.fc); rows 0 .. 3 of
+   vals[DRAGG_NEVV][M] are their entry 0 */
+enum dragg_ev_key {
+    DRAGG_EVK_P_CH = 0,         /* p_ev_ch    = ch_k                                        */
+    DRAGG_EVK_P_DISCH,          /* p_ev_disch = dis_k (<= 0)                                */
+    DRAGG_EVK_E,                /* e_ev_opt   = E_{k+1}: vals' row is the next step's E_0   */
+    DRAGG_EVK_COST,             /* cost_ev    = price_k S (ch_k + dis_k), as cost_opt       */
+    DRAGG_NEVK
+};
+enum dragg_ev_val {
+    DRAGG_EVV_FORECAST_P = DRAGG_NEVK,   /* forecast_p_ev = ch_1 + dis_1 (0 at H == 1)      */
+    DRAGG_NEVV
+};
+enum dragg_ev_status {
+    DRAGG_EV_OPTIMAL = 0,       /* the LP's optimum                                          */
+    DRAGG_EV_INFEASIBLE = 1     /* no trajectory: the uncontrolled rule's rows (below)       */
+};
+
+typedef struct dragg_mpc_ev {
+    const double* params;       /* [DRAGG_NEVP][M]                                           */
+    double* vals;               /* [DRAGG_NEVV][M] in/out (the step reads row DRAGG_EVK_E at t > 0) */
+    double* fc;                 /* [M][DRAGG_NEVK][H] out                                    */
+    int32_t* status;            /* [M] dragg_ev_status                                       */
+    double* obj;                /* [M] sum_k q_k (ch_k + dis_k), summed in ascending k without contraction; */
+                                /* NaN where infeasible                                      */
+    int32_t day_offset;         /* step of day of timestep 0, 0 .. 24 dt - 1                 */
+    int32_t n_vehicles;         /* M (0: every entry is a no-op, the sums are zero)          */
+} dragg_mpc_ev;
+
+/* explicit per-stage inputs: the general storage LP (parity tests).  Row k of lo / hi is the box of E_{k+1}. */
+typedef struct dragg_mpc_ev_explicit {
+    const double* price;        /* [H][M] price_k (q_k = S gamma^k price_k)                  */
+    const double* rate_ch;      /* [H][M] >= 0                                               */
+    const double* rate_dis;     /* [H][M] >= 0                                               */
+    const double* drain;        /* [H][M]                                                    */
+    const double* lo;           /* [H][M]                                                    */
+    const double* hi;           /* [H][M]                                                    */
+    const double* E0;           /* [M]                                                       */
+} dragg_mpc_ev_explicit;
+
+/* dynamic LDS of one EV workgroup (DRAGG_EV_WAVES vehicles), or DRAGG_E_HORIZON / DRAGG_E_ARG */
+#define DRAGG_EV_WAVES 4
+int dragg_mpc_ev_lds_bytes(const dragg_mpc_dims* dims);
+
+/* Solve every vehicle's LP on the explicit inputs; reads params rows ETAC, ETAD (the dynamics) and EMAX, CAP (the
+   uncontrolled rule) and writes vals, fc, status, obj.  An infeasible LP gets the uncontrolled rule, evaluated
+   on one lane in ascending k without contraction:
+       ch_k = min(rate_ch_k, max(0, (Emax - E) / a)),  dis_k = 0,  E <- min(max((E + a ch_k) - drain_k, 0), capacity).
+   DRAGG_E_ARG for G > 1 (explicit inputs carry no price rows). */
+int dragg_mpc_ev_solve_explicit(const dragg_mpc_dims* dims, const dragg_mpc_ev* ev,
+                                const dragg_mpc_ev_explicit* in, void* stream);
+
+/* One closed-loop step: the kernel builds the explicit inputs itself -- stage k lies at step of day
+   s_k = (day_offset + t + k) mod 24 dt; away iff depart <= s_k < return; rate_ch_k = away ? 0 : max_rate,
+   rate_dis_k = v2g ? rate_ch_k : 0, drain_k = away ? trip / (return - depart) : 0, the box of E_{k+1} is
+   [s_{k+1} == depart ? max(Emin, Ereq) : Emin, Emax], price_k = reward_price[k] + tou[start_index + t + k] (the
+   home prologue's expression; group g reads row g of problem.reward_price), E_0 = params EINIT at t == 0, else
+   vals row DRAGG_EVK_E -- and runs dragg_mpc_ev_solve_explicit's code on them.  Reads problem.tou,
+   reward_price and start_index only. */
+int dragg_mpc_ev_step(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, const dragg_mpc_ev* ev,
+                      int32_t timestep, void* stream);
+
+/* The vehicles' part of collect_data's sums per group: out[g] = [sum (ch_0 + dis_0), sum forecast_p_ev,
+   sum cost_ev_0] over group g's M / G vehicles.  One 1024-thread block per group: thread i adds vehicles i,
+   i + 1024, ... of the group in ascending order, the 64 lanes of a wave are added in the fixed order of the wave
+   sum, the 16 wave partials pairwise as a balanced tree -- an order that depends on neither G nor the batch
+   around the group, so a group's sums are those of a fleet of its vehicles alone, bit for bit.  No contraction,
+   no atomics.  M == 0: zeros. */
+int dragg_mpc_ev_aggregate(const dragg_mpc_dims* dims, const dragg_mpc_ev* ev, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
