@@ -5,8 +5,8 @@
 // mpc_direct_kernel) solves it exactly -- the two thermal integer chains by a forward
 // Pareto-front DP (dp_front: labels (state, cost) with dominance filters on two bucket grids,
 // optionally pruned by an LP cost-to-go bound), the battery LP by an exact convex
-// piecewise-linear DP (battery_lp), PV curtailment in closed form -- in a first launch
-// (DM_FRONT); homes whose chains leave the front DP's scope (front overflow, mixed-sign prices
+// piecewise-linear DP (storage_lp, the one recursion that the vehicle kernel ev_kernel runs too),
+// PV curtailment in closed form -- in a first launch (DM_FRONT); homes whose chains leave the front DP's scope (front overflow, mixed-sign prices
 // without a usable bound) are finished by a second launch (DM_BUCKET) with the bucketed DP.
 // int_mode relax / round_lp (mpc_home_kernel) solve the LP relaxation by an OSQP-style ADMM
 // whose block-tridiagonal KKT factor lives in LDS, with an exact basis polish every
@@ -24,6 +24,7 @@
 #include "../../include/dragg_mi355x.h"
 
 #define DEV static __device__ __forceinline__
+#define MDEV __device__ __forceinline__       // ... of a member function
 
 // sha-256 of this file and the header, stamped by dragg_amd/build.py (-DDRAGG_SOURCE_HASH): the host
 // refuses a library whose stamp differs from the sources beside it (dragg_amd/_lib.py); the prefix lets
@@ -1553,19 +1554,24 @@ __global__ __launch_bounds__(64) void mpc_home_kernel(KArgs a) {
 // (E, ch, dis) and the PV curtailment.  So the MILP optimum is
 //   thermal integer programme (two integer chains)      -> binned forward DP  (dp_thermal)
 // + battery LP (one continuous storage chain)            -> exact convex piecewise-linear
-//                                                           value-function DP (battery_lp)
+//                                                           value-function DP (storage_lp)
 // + PV LP (separable per stage)                          -> closed form        (pv_curt)
 // No relaxation / ADMM is needed on this path; the LP kernel above remains the solver of
 // the relaxation (int_mode relax) and of the relaxation-then-round variant (round_lp).
 // ======================================================================================
 
-struct LdsD {
+// storage_lp's scratch: what LdsD and EvLds hand to it
+struct StorageScratch {
+    double *sgS, *sgL;                  // segment lists [2][seg_cap]: slopes, lengths
+    double *bx0, *bp1, *bp2;            // [H] recovery: merged-domain origin, offsets of psi's two segments
+};
+
+struct LdsD : StorageScratch {          // (the battery's lists in lab / rmin: it runs after the thermal DPs)
     double *draw, *oat, *ghi, *price;   // [H+1]
     double *x;                          // [8H] solution in the stage-slot layout of the LP path
     double *t2;                         // [H] p_grid (objective)
     double *cA, *cC, *cq;               // [H] coefficients of the chain being solved
     double *sc;                         // [32] scalars / reduction scratch
-    double *bx0, *bp1, *bp2;            // [H] battery: merged-domain origin, psi segment offsets
     double2 *lab;                       // [NB_CAP] DP labels (dp_front: front A (key, cost);
                                         //   dp_zspace / dp_fixed: (cost, exact state))
     double2 *rmin;                      // [NB_CAP+8] dp_front: front B; dp_zspace: cheapest
@@ -1578,8 +1584,6 @@ struct LdsD {
     double *rt;                         // [H+2] zero-duty reference trajectory of the chain
     int *candp;                         // [NBND][S+1] candidate records
     int16_t *tarr, *rsrc;               // [NB_CAP], [NB_CAP+8] source keys, source of rmin
-    double *sgS, *sgL;                  // battery segments [2][seg_cap], in lab / rmin (the
-                                        //   battery LP runs after the thermal DPs)
     double* wl;                         // [3][WAVE] dp_front's W table (points, values, slopes)
     char* xch;                          // [xch_bytes(cap)] a multi-wave DP's exchange area
     uint16_t* par;                      // [H][NB_CAP] DP back-pointers (global workspace)
@@ -3614,40 +3618,74 @@ DEV bool round_duties(const Home& h, const Lds& L, int lane, uint16_t* par) {
 }
 
 // --------------------------------------------------------------------------------------
-// Battery LP (mpc_calc.py:355-373 with its p_grid / cost terms): min sum_k q_k (ch_k + dis_k),
-// E_{k+1} = E_k + a ch_k + b dis_k (a = eta_c/dt, b = 1/(eta_d dt)), 0 <= ch <= r,
-// -r <= dis <= 0, Emin <= E_{1..H} <= Emax, q_k = S gamma^k price_k.
+// Storage LP (storage_lp): the one recursion under the home's battery (mpc_calc.py:355-373 with its
+// p_grid / cost terms) and the electric vehicle (dragg_mpc_ev_*):
+//   min sum_k q_k (ch_k + dis_k),  E_{k+1} = E_k + a ch_k + b dis_k - drain_k  (a = eta_c/dt,
+//   b = 1/(eta_d dt)),  0 <= ch_k <= rc_k,  -rd_k <= dis_k <= 0,  lo_k <= E_{k+1} <= hi_k,
+//   q_k = S gamma^k price_k.
 // The cost-to-go V_k(E) is convex piecewise linear.  With psi_k(z) the cheapest cost of
 // moving E_k -> E_k - z in one stage (two linear pieces: charge / discharge, or for q < 0
-// the charge-while-discharging edge), V_k = clip(V_{k+1} [inf-convolution] psi_k): the
-// sorted (slope, length) segment list of V_{k+1} merged with psi_k's two segments, then
-// cut to [Emin, Emax].  Each stage is a rank count + a scatter + a prefix scan on one wave.
+// the charge-while-discharging edge), V_k(E) = min_z psi_k(z) + V_{k+1}(E - z - drain_k), cut
+// to stage k's box: the sorted (slope, length) segment list of V_{k+1} merged with psi_k's two
+// segments, its origin moved by drain_k, then cut.  Each stage is a rank count + a scatter + a
+// prefix scan on one wave.
 // Recovery needs, per stage, only the merged domain origin and the offsets of psi_k's two
 // segments in the merged order: the optimal split of a position p along the merged list
 // takes psi's share of the first p units of length.  Exact, no iteration.
 // Runs on one wave; at most 2H + 1 segments.
+//
+// The problem comes in as a stage view (BatteryStages here, EvStages by the vehicle kernel):
+//   H, a, b, E0;  q(k), rc(k), rd(k), lo(k), hi(k) (the box of E_{k+1}), drain(k) where DRAINS;
+//   mul(x, y): the products a rc_k and b rd_k (they stand next to adds only where the rates
+//     change by stage, and there they must not be contracted into them).  a rc_k is subtracted
+//     where psi_k's origin -a rc_k is meant, never negated and added: the compiler rebuilds a
+//     negated product that feeds one add with that add's flags, contraction among them;
+//   STAGE_BOX: the box is the caller's per stage and may be empty, so the terminal one is checked;
+//   ONE_RATE: rc_k = rd_k = one loop invariant.  psi's two lengths are then (b or a) r, a choice and
+//     one multiply -- the code the hot launch has always had and was measured with; with rates per
+//     stage they are chosen from a rc_k and b rd_k, the vehicle kernel's code as it was measured.
+//     The same numbers either way;
+//   next(k, E, ch, dis): the state update of the recovery;  store(k, ch, dis, E): where a stage goes.
+// With rc = rd = r, no drain and one box a view gives the battery's arithmetic to the bit,
+// whichever view it is (tests/test_gpu_ev.py pins EvStages against BatteryStages there).
 // --------------------------------------------------------------------------------------
-DEV void battery_psi(const Home& h, double q, double* s1, double* l1, double* s2, double* l2) {
-    const double a = h.etac / h.dt, b = (1.0 / h.etad) / h.dt, r = h.brate;
-    if (q >= 0.0) { *s1 = -q / a; *l1 = a * r; *s2 = -q / b; *l2 = b * r; }   // charge | discharge
-    else          { *s1 = -q / b; *l1 = b * r; *s2 = -q / a; *l2 = a * r; }   // full-charge edge first
+template <class View>
+DEV void storage_psi(const View& V, double q, double rc, double rd, double ar,
+                     double* s1, double* l1, double* s2, double* l2) {
+    const bool edge = !(q >= 0.0);                              // charge | discharge; else the full-charge edge first
+    const double c1 = edge ? V.b : V.a, c2 = edge ? V.a : V.b;  // the coefficient of psi's first and second piece
+    *s1 = -q / c1;
+    *s2 = -q / c2;
+    if constexpr (View::ONE_RATE) {                             // rc = rd, a loop invariant: its pieces' lengths
+        *l1 = V.mul(c1, rc); *l2 = V.mul(c2, rc);               //   are one multiply each after the choice
+    } else {                                                    // else a rc_k exists anyway (the origin's) and
+        const double br = V.mul(V.b, rd);                       //   the two products are chosen from
+        *l1 = edge ? br : ar; *l2 = edge ? ar : br;
+    }
 }
 
-DEV bool battery_lp(const Home& h, LdsD& L, int lane) {
-    const int H = h.H;
+template <class View>
+DEV bool storage_lp(const View& V, const StorageScratch& W, int lane) {
+    const int H = V.H;
     const int cap = seg_cap(H);
-    const double a = h.etac / h.dt, b = (1.0 / h.etad) / h.dt, r = h.brate;
-    const double x0psi = -a * r;
-    double* S0 = L.sgS;  double* L0 = L.sgL;          // current list
-    double* S1 = L.sgS + cap; double* L1 = L.sgL + cap;
+    const double a = V.a, b = V.b;
+    double* S0 = W.sgS;  double* L0 = W.sgL;          // current list
+    double* S1 = W.sgS + cap; double* L1 = W.sgL + cap;
     int n = 1;
-    double x0 = h.Emin;                               // V_H: free terminal state, slope 0
-    if (lane == 0) { S0[0] = 0.0; L0[0] = h.Emax - h.Emin; }
+    double x0 = V.lo(H - 1);                          // V_H: free inside the last box, slope 0
+    double len = V.hi(H - 1) - x0;
+    if constexpr (View::STAGE_BOX) {
+        if (!(x0 <= V.hi(H - 1) + TOL_P * (1 + fabs(V.hi(H - 1))))) return false;
+        len = fmax(0.0, len);
+    }
+    if (lane == 0) { S0[0] = 0.0; L0[0] = len; }
     wave_sync();
     bool feasible = true;
     for (int k = H - 1; k >= 0; --k) {
+        const double r = V.rc(k), rd = V.rd(k);
+        const double ar = V.mul(a, r);                // psi_k's domain starts at -a rc_k (subtracted: see above)
         double s1, l1, s2, l2;
-        battery_psi(h, L.cq[k], &s1, &l1, &s2, &l2);
+        storage_psi(V, V.q(k), r, rd, ar, &s1, &l1, &s2, &l2);
         // ranks: psi's segments go after existing segments of equal slope
         int c1 = 0, c2 = 0;
         double p1 = 0.0, p2 = 0.0;
@@ -3666,21 +3704,23 @@ DEV bool battery_lp(const Home& h, LdsD& L, int lane) {
             S1[j] = si; L1[j] = L0[i];
         }
         if (lane == 0) { S1[r1] = s1; L1[r1] = l1; S1[r2] = s2; L1[r2] = l2; }
-        const double X0M = x0 + x0psi;
-        if (lane == 0) { L.bx0[k] = X0M; L.bp1[k] = p1; L.bp2[k] = p2; }
+        double X0M = x0 - ar;
+        if constexpr (View::DRAINS) X0M += V.drain(k);          // E_k = E_{k+1} + z + drain_k
+        if (lane == 0) { W.bx0[k] = X0M; W.bp1[k] = p1; W.bp2[k] = p2; }
         n += 2;
         wave_sync();
         double tot = 0.0;
         for (int i = lane; i < n; i += WAVE) tot += L1[i];
         tot = dpp_sum(tot);
         if (k == 0) {                                 // E_0 is fixed: it must lie in the domain
-            const double p = h.E0 - X0M;
-            feasible = p >= -TOL_P * (1 + fabs(h.E0)) && p <= tot + TOL_P * (1 + fabs(h.E0));
+            const double p = V.E0 - X0M;
+            feasible = p >= -TOL_P * (1 + fabs(V.E0)) && p <= tot + TOL_P * (1 + fabs(V.E0));
             break;
         }
-        // cut the merged list to E_k in [Emin, Emax] (k >= 1)
-        const double cl = fmax(0.0, h.Emin - X0M), chi = fmin(tot, h.Emax - X0M);
-        if (!(cl <= chi + TOL_P * (1 + fabs(h.Emax)))) { feasible = false; break; }
+        // cut the merged list to E_k's box (k >= 1: that of stage k - 1)
+        const double blo = V.lo(k - 1), bhi = V.hi(k - 1);
+        const double cl = fmax(0.0, blo - X0M), chi = fmin(tot, bhi - X0M);
+        if (!(cl <= chi + TOL_P * (1 + fabs(bhi)))) { feasible = false; break; }
         // exclusive prefix of lengths in list order (lane-contiguous chunks)
         const int per = (n + WAVE - 1) / WAVE;
         const int i0 = lane * per, i1 = min(n, i0 + per);
@@ -3708,30 +3748,56 @@ DEV bool battery_lp(const Home& h, LdsD& L, int lane) {
     }
     if (!feasible) return false;
     if (lane == 0) {                                  // forward recovery of E, ch, dis
-        double E = h.E0;
+        double E = V.E0;
         for (int k = 0; k < H; ++k) {
+            const double r = V.rc(k), rd = V.rd(k), q = V.q(k);
+            const double ar = V.mul(a, r);
             double s1, l1, s2, l2;
-            battery_psi(h, L.cq[k], &s1, &l1, &s2, &l2);
-            const double p = E - L.bx0[k];
-            const double z = x0psi + fmin(fmax(p - L.bp1[k], 0.0), l1) + fmin(fmax(p - L.bp2[k], 0.0), l2);
-            const double dlt = -z;                   // E_{k+1} - E_k
+            storage_psi(V, q, r, rd, ar, &s1, &l1, &s2, &l2);
+            const double p = E - W.bx0[k];
+            const double z = fmin(fmax(p - W.bp1[k], 0.0), l1) - ar + fmin(fmax(p - W.bp2[k], 0.0), l2);
+            const double dlt = -z;                   // a ch_k + b dis_k
             double chv, dis;
-            if (L.cq[k] >= 0.0) {
+            if (q >= 0.0) {
                 if (dlt >= 0.0) { chv = fmin(dlt / a, r); dis = 0.0; }
-                else            { chv = 0.0; dis = fmax(dlt / b, -r); }
+                else            { chv = 0.0; dis = fmax(dlt / b, -rd); }
             } else {
-                chv = fmin(r, (dlt + b * r) / a);
-                dis = fmax(-r, fmin(0.0, (dlt - a * chv) / b));
+                chv = fmin(r, (dlt + V.mul(b, rd)) / a);
+                dis = fmax(-rd, fmin(0.0, (dlt - a * chv) / b));
             }
-            E = E + (h.etac * chv + dis / h.etad) / h.dt;   // mpc_calc.py:363-365
-            L.x[k * 8 + S_CH] = chv;
-            L.x[k * 8 + S_DIS] = dis;
-            L.x[k * 8 + S_E] = E;
+            E = V.next(k, E, chv, dis);
+            V.store(k, chv, dis, E);
         }
     }
     wave_sync();
     return true;
 }
+
+// the home's battery: one rate, one box (Emin <= E <= Emax), no drain; the cost row is L.cq
+struct BatteryStages {
+    static constexpr bool DRAINS = false, STAGE_BOX = false, ONE_RATE = true;
+    const Home& h;
+    const LdsD& L;
+    const int H;
+    const double a, b, E0;
+    MDEV BatteryStages(const Home& h_, const LdsD& L_)
+        : h(h_), L(L_), H(h_.H), a(h_.etac / h_.dt), b((1.0 / h_.etad) / h_.dt), E0(h_.E0) {}
+    MDEV double q(int k) const { return L.cq[k]; }
+    MDEV double rc(int) const { return h.brate; }
+    MDEV double rd(int) const { return h.brate; }
+    MDEV double lo(int) const { return h.Emin; }
+    MDEV double hi(int) const { return h.Emax; }
+    MDEV static double mul(double x, double y) { return x * y; }   // (loop invariants: hoisted, never fused)
+    MDEV double next(int, double E, double chv, double dis) const {
+        return E + (h.etac * chv + dis / h.etad) / h.dt;           // mpc_calc.py:363-365
+    }
+    MDEV void store(int k, double chv, double dis, double E) const {
+        L.x[k * 8 + S_CH] = chv;
+        L.x[k * 8 + S_DIS] = dis;
+        L.x[k * 8 + S_E] = E;
+    }
+};
+
 
 // --------------------------------------------------------------------------------------
 // EXACT thermal chain DP without any dominance assumption: backward step functions (dp_steps).
@@ -4845,7 +4911,7 @@ DEV void solve_direct(const KArgs& a, int home, double* smem, int slot, int firs
             for (int k = lane; k < H; k += NT) D.cq[k] = pow(h.gamma, (double)k) * D.price[k] * h.S;
             __syncthreads();
             bool bok = true;
-            if (lane < WAVE) bok = battery_lp(h, D, lane);
+            if (lane < WAVE) bok = storage_lp(BatteryStages(h, D), D, lane);
             if (lane == 0) D.sc[31] = bok ? 1.0 : 0.0;
             __syncthreads();
             if (D.sc[31] == 0.0) status = DRAGG_ST_INFEASIBLE;
@@ -5520,10 +5586,9 @@ __global__ void noise_kernel(int N, int H, dragg_mpc_episodes ep, uint64_t seed,
 // Electric vehicles (dragg_mpc_ev_*): the stage-varying storage LP
 //   min sum_k q_k (ch_k + dis_k),  E_{k+1} = E_k + a ch_k + b dis_k - drain_k,  0 <= ch_k <= rc_k,
 //   -rd_k <= dis_k <= 0,  lo_k <= E_{k+1} <= hi_k,  q_k = S gamma^k price_k.
-// battery_lp's recursion with per-stage arrays: psi_k from (rc_k, rd_k), the merged domain origin
-// x0 + x0psi_k + drain_k (V_k(E) = min_z psi_k(z) + V_{k+1}(E - z - drain_k)), the cut to stage k's own box;
-// recovery forward as there.  The expressions keep battery_lp's shapes, so that with rc = rd = r, drain = 0 and
-// a constant box the arithmetic is battery_lp's to the bit.  One wave per vehicle, EV_WAVES vehicles per
+// solved by storage_lp, the recursion of the home's battery, through a stage view whose every quantity is a
+// per-stage row in LDS (EvStages): psi_k from (rc_k, rd_k), the merged domain origin x0 + x0psi_k + drain_k, the
+// cut to stage k's own box.  One wave per vehicle, EV_WAVES vehicles per
 // workgroup, each with its own slice of the dynamic LDS; the waves never meet (wave_sync only: a wave past the
 // last vehicle simply leaves).
 // --------------------------------------------------------------------------------------
@@ -5532,10 +5597,8 @@ constexpr int EV_NT = EV_WAVES * WAVE;
 constexpr int EV_ROWS = 13;
 __host__ __device__ inline int ev_lds_doubles(int H) { return 4 * seg_cap(H) + EV_ROWS * H; }
 
-struct EvLds {
-    double *sgS, *sgL;                      // segment lists [2][seg_cap]: slopes, lengths
+struct EvLds : StorageScratch {
     double *pi, *q, *rc, *rd, *dr, *lo, *hi; // [H] price, cost row, rates, drain, the box of E_{k+1}
-    double *bx0, *bp1, *bp2;                // [H] recovery: merged origin, offsets of psi's segments
     double *ch, *dis, *E;                   // [H] the trajectory (E[k] = E_{k+1})
 };
 struct EvCar {
@@ -5562,124 +5625,38 @@ DEV EvLds ev_carve(double* s, int H) {
     return L;
 }
 
-// a product that is never contracted into a following add.  battery_lp's a r and b r are loop invariants, computed
-// before its loops, so no add of its loops fuses with them; here the rates change by stage and the products stand
-// next to those adds
-DEV double ev_mul(double x, double y) {
+// the vehicle as storage_lp's stage view: every stage quantity is a row of EvLds
+struct EvStages {
+    static constexpr bool DRAINS = true, STAGE_BOX = true, ONE_RATE = false;
+    const EvCar& c;
+    const EvLds& L;
+    const int H;
+    const double a, b, E0;
+    MDEV EvStages(const EvCar& c_, const EvLds& L_)
+        : c(c_), L(L_), H(c_.H), a(c_.etac / c_.dt), b((1.0 / c_.etad) / c_.dt), E0(c_.E0) {}
+    MDEV double q(int k) const { return L.q[k]; }
+    MDEV double rc(int k) const { return L.rc[k]; }
+    MDEV double rd(int k) const { return L.rd[k]; }
+    MDEV double lo(int k) const { return L.lo[k]; }
+    MDEV double hi(int k) const { return L.hi[k]; }
+    MDEV double drain(int k) const { return L.dr[k]; }
+    // a product that is never contracted into a following add.  The battery's a r and b r are loop invariants,
+    // computed before storage_lp's loops, so no add of its loops fuses with them; here the rates change by stage
+    // and the products stand next to those adds
+    MDEV static double mul(double x, double y) {
 #pragma clang fp contract(off)
-    return x * y;
-}
-DEV void ev_psi(double a, double b, double q, double rc, double rd, double* s1, double* l1, double* s2, double* l2) {
-    const double ar = ev_mul(a, rc), br = ev_mul(b, rd);
-    if (q >= 0.0) { *s1 = -q / a; *l1 = ar; *s2 = -q / b; *l2 = br; }   // charge | discharge
-    else          { *s1 = -q / b; *l1 = br; *s2 = -q / a; *l2 = ar; }   // full-charge edge first
-}
+        return x * y;
+    }
+    MDEV double next(int k, double E, double chv, double dis) const {
+        return E + (c.etac * chv + dis / c.etad) / c.dt - L.dr[k];
+    }
+    MDEV void store(int k, double chv, double dis, double E) const {
+        L.ch[k] = chv;
+        L.dis[k] = dis;
+        L.E[k] = E;
+    }
+};
 
-DEV bool ev_lp(const EvCar& c, const EvLds& L, int lane) {
-    const int H = c.H;
-    const int cap = seg_cap(H);
-    const double a = c.etac / c.dt, b = (1.0 / c.etad) / c.dt;
-    double* S0 = L.sgS;  double* L0 = L.sgL;          // current list
-    double* S1 = L.sgS + cap; double* L1 = L.sgL + cap;
-    int n = 1;
-    double x0 = L.lo[H - 1];                          // V_H: free inside the last box, slope 0
-    const double hiH = L.hi[H - 1];
-    if (!(x0 <= hiH + TOL_P * (1 + fabs(hiH)))) return false;
-    if (lane == 0) { S0[0] = 0.0; L0[0] = fmax(0.0, hiH - x0); }
-    wave_sync();
-    bool feasible = true;
-    for (int k = H - 1; k >= 0; --k) {
-        const double r = L.rc[k], rd = L.rd[k];
-        const double x0psi = -ev_mul(a, r);
-        double s1, l1, s2, l2;
-        ev_psi(a, b, L.q[k], r, rd, &s1, &l1, &s2, &l2);
-        // ranks: psi's segments go after existing segments of equal slope
-        int c1 = 0, c2 = 0;
-        double p1 = 0.0, p2 = 0.0;
-        for (int i = lane; i < n; i += WAVE) {
-            const double si = S0[i], li = L0[i];
-            if (si <= s1) { ++c1; p1 += li; }
-            if (si <= s2) { ++c2; p2 += li; }
-        }
-        c1 = dpp_isum(c1); c2 = dpp_isum(c2);
-        p1 = dpp_sum(p1); p2 = dpp_sum(p2);
-        const int r1 = c1, r2 = c2 + 1;               // merged positions of psi's segments
-        p2 += l1;                                     // psi 1 precedes psi 2 (s1 <= s2)
-        for (int i = lane; i < n; i += WAVE) {
-            const double si = S0[i];
-            const int j = i + (s1 < si ? 1 : 0) + (s2 < si ? 1 : 0);
-            S1[j] = si; L1[j] = L0[i];
-        }
-        if (lane == 0) { S1[r1] = s1; L1[r1] = l1; S1[r2] = s2; L1[r2] = l2; }
-        const double X0M = x0 + x0psi + L.dr[k];      // E_k = E_{k+1} + z + drain_k
-        if (lane == 0) { L.bx0[k] = X0M; L.bp1[k] = p1; L.bp2[k] = p2; }
-        n += 2;
-        wave_sync();
-        double tot = 0.0;
-        for (int i = lane; i < n; i += WAVE) tot += L1[i];
-        tot = dpp_sum(tot);
-        if (k == 0) {                                 // E_0 is fixed: it must lie in the domain
-            const double p = c.E0 - X0M;
-            feasible = p >= -TOL_P * (1 + fabs(c.E0)) && p <= tot + TOL_P * (1 + fabs(c.E0));
-            break;
-        }
-        // cut the merged list to E_k's own box (k >= 1: row k - 1)
-        const double blo = L.lo[k - 1], bhi = L.hi[k - 1];
-        const double cl = fmax(0.0, blo - X0M), chi = fmin(tot, bhi - X0M);
-        if (!(cl <= chi + TOL_P * (1 + fabs(bhi)))) { feasible = false; break; }
-        // exclusive prefix of lengths in list order (lane-contiguous chunks)
-        const int per = (n + WAVE - 1) / WAVE;
-        const int i0 = lane * per, i1 = min(n, i0 + per);
-        double loc = 0.0;
-        for (int i = i0; i < i1; ++i) loc += L1[i];
-        const double inc = dpp_scan(loc, lane);
-        double pre = inc - loc;
-        int first = n, last = -1;
-        for (int i = i0; i < i1; ++i) {
-            const double st = pre, en = pre + L1[i];
-            const double ns = fmax(st, cl), ne = fmin(en, chi);
-            if (ne > ns) { first = min(first, i); last = max(last, i); }
-            L1[i] = fmax(0.0, ne - ns);
-            pre = en;
-        }
-        first = dpp_imin(first);
-        last = dpp_imax(last);
-        wave_sync();
-        const int nn = last >= first ? last - first + 1 : 0;
-        for (int i = lane; i < nn; i += WAVE) { S0[i] = S1[first + i]; L0[i] = L1[first + i]; }
-        if (nn == 0 && lane == 0) { S0[0] = 0.0; L0[0] = 0.0; }   // a single feasible point
-        n = nn == 0 ? 1 : nn;
-        x0 = X0M + cl;
-        wave_sync();
-    }
-    if (!feasible) return false;
-    if (lane == 0) {                                  // forward recovery of E, ch, dis
-        double E = c.E0;
-        for (int k = 0; k < H; ++k) {
-            const double r = L.rc[k], rd = L.rd[k], qk = L.q[k];
-            const double x0psi = -ev_mul(a, r);
-            double s1, l1, s2, l2;
-            ev_psi(a, b, qk, r, rd, &s1, &l1, &s2, &l2);
-            const double p = E - L.bx0[k];
-            const double z = x0psi + fmin(fmax(p - L.bp1[k], 0.0), l1) + fmin(fmax(p - L.bp2[k], 0.0), l2);
-            const double dlt = -z;                   // a ch_k + b dis_k
-            double chv, dis;
-            if (qk >= 0.0) {
-                if (dlt >= 0.0) { chv = fmin(dlt / a, r); dis = 0.0; }
-                else            { chv = 0.0; dis = fmax(dlt / b, -rd); }
-            } else {
-                chv = fmin(r, (dlt + ev_mul(b, rd)) / a);
-                dis = fmax(-rd, fmin(0.0, (dlt - a * chv) / b));
-            }
-            E = E + (c.etac * chv + dis / c.etad) / c.dt - L.dr[k];
-            L.ch[k] = chv;
-            L.dis[k] = dis;
-            L.E[k] = E;
-        }
-    }
-    wave_sync();
-    return true;
-}
 
 // the uncontrolled rule (no trajectory), one lane, ascending k; contraction off, so that the same operations in
 // the same order on the host give the same bits
@@ -5765,7 +5742,7 @@ __global__ __launch_bounds__(EV_NT) void ev_kernel(EvArgs a) {
     // the home kernel's battery cost row, expression for expression
     for (int k = lane; k < H; k += WAVE) L.q[k] = pow(c.gamma, (double)k) * L.pi[k] * c.S;
     wave_sync();
-    const bool ok = ev_lp(c, L, lane);
+    const bool ok = storage_lp(EvStages(c, L), L, lane);
     double obj = __builtin_nan("");
     if (lane == 0) {
         if (ok) obj = ev_objective(L, H);

@@ -10,8 +10,9 @@ programme, the PV LP and this block:
 
 E_0 fixed and not boxed.  It is solved here as a sparse LP by scipy's HiGHS with the primal and
 dual feasibility tolerances at 1e-10: the independent checker of the GPU's piecewise-linear
-value-function DP (`battery_lp` in dragg_amd/csrc/mpc_kernel.hip), which shares nothing with
-it but the statement above.  `dragg_amd` never imports this module.
+value-function DP (`storage_lp` in dragg_amd/csrc/mpc_kernel.hip, the one recursion under the
+battery and the vehicle, here through its battery view), which shares nothing with it but the
+statement above.  `dragg_amd` never imports this module.
 """
 from dataclasses import dataclass
 

@@ -1,4 +1,7 @@
-"""Hard battery and PV cases for the default path's battery LP (`battery_lp`) and PV rule (`pv_curt`).
+"""Hard battery and PV cases for the default path's battery LP and PV rule (`pv_curt`).
+
+The battery LP is the kernel's one storage recursion, `storage_lp`, through its battery view (the
+vehicle of tests/ev_cases.py runs the same body through the other view).
 
 One deterministic generator, shared by tests/test_oracle_battery.py (CPU: the reference and the
 generator's own conditions) and tests/test_gpu_battery.py (the kernel against the reference).  A

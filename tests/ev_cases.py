@@ -1,4 +1,7 @@
-"""Hard cases for the EV storage LP (`ev_lp` in dragg_amd/csrc/mpc_kernel.hip) and its independent reference.
+"""Hard cases for the EV storage LP and its independent reference.
+
+The kernel side is `storage_lp` in dragg_amd/csrc/mpc_kernel.hip, the one recursion under the home's battery and
+the vehicle, here through the vehicle's stage view (per-stage rates, drain and box).
 
 One deterministic generator, shared by tests/test_ev_host.py (CPU: the reference pinned, the generator's own
 conditions, a float64 restatement of the kernel's recursion) and tests/test_gpu_ev.py (the kernel against the

@@ -1,4 +1,5 @@
-"""The kernel's battery LP (`battery_lp`) and PV rule (`pv_curt`) against an independent LP.
+"""The kernel's battery LP (`storage_lp` through its battery view) and PV rule (`pv_curt`) against an
+independent LP.  `storage_lp` is the one recursion under the battery and the vehicle (test_gpu_ev.py).
 
 The default path (int_mode round) solves every battery home's storage problem with a one-wave
 piecewise-linear value-function DP whose segment lists alias the thermal DP's dead LDS buffers.

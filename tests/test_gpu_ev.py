@@ -1,4 +1,5 @@
-"""The EV storage LP kernel (`ev_lp`, dragg_mpc_ev_*) on the GPU: against the independent LP of
+"""The EV storage LP kernel (`storage_lp` through the vehicle's stage view, dragg_mpc_ev_*) on the GPU -- the one
+recursion that also solves the home's battery, through the battery's view: against the independent LP of
 tests/ev_cases.py, against the home kernel's battery LP on the degenerate vehicle, the closed-loop step against
 the explicit entry, groups, and the entries' edges.
 
@@ -103,7 +104,8 @@ def test_fallback_rows_equal_the_numpy_rule(H, gpu):
 
 @pytest.mark.parametrize("batch", BC.BATCHES, ids=BC.batch_id)
 def test_degenerate_vehicle_is_the_battery(batch, gpu):
-    """An always-home, zero-trip, v2g vehicle with Ereq <= Emin is the home kernel's battery LP: on the cases of
+    """The two stage views of the one recursion agree where they state the same problem.  An always-home,
+    zero-trip, v2g vehicle with Ereq <= Emin is the home kernel's battery LP: on the cases of
     tests/battery_cases.py the explicit EV entry's p_ev_ch, p_ev_disch and e_ev_opt equal the home kernel's
     p_batt_ch, p_batt_disch and e_batt_opt bit for bit at every home whose status is optimal, and the vehicle is
     infeasible exactly where the home is not optimal.  On the discount = 1 batches the reported objective equals the
