@@ -257,7 +257,8 @@ EXPORTS = ["dragg_mpc_abi_version", "dragg_mpc_strerror", "dragg_mpc_lds_bytes",
            "dragg_mpc_season_noise_episodes", "dragg_mpc_adopt", "dragg_mpc_select_groups", "dragg_mpc_env_file",
            "dragg_mpc_env_reset", "dragg_mpc_plan_groups", "dragg_mpc_select_paths", "dragg_mpc_step_classes",
            "dragg_mpc_plan_classes", "dragg_mpc_ev_lds_bytes", "dragg_mpc_ev_solve_explicit", "dragg_mpc_ev_step",
-           "dragg_mpc_ev_aggregate"]
+           "dragg_mpc_ev_aggregate", "dragg_mpc_ev_step_episodes", "dragg_mpc_ev_aggregate_onto", "dragg_mpc_ev_adopt",
+           "dragg_mpc_ev_reset"]
 
 _LIB = None
 
@@ -341,6 +342,12 @@ def load(path=LIB_PATH):
     lib.dragg_mpc_ev_step.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Problem), ctypes.POINTER(Ev), ctypes.c_int32,
                                       c_dp]
     lib.dragg_mpc_ev_aggregate.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ev), c_dp, c_dp]
+    lib.dragg_mpc_ev_step_episodes.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Problem), ctypes.POINTER(Episodes),
+                                               ctypes.POINTER(Classes), ctypes.POINTER(Ev), ctypes.c_int32, c_dp]
+    lib.dragg_mpc_ev_aggregate_onto.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ev), c_dp, c_dp, c_dp, c_dp]
+    lib.dragg_mpc_ev_adopt.argtypes = [ctypes.POINTER(Dims), ctypes.c_int32, c_dp, ctypes.POINTER(Ev),
+                                       ctypes.POINTER(Ev), c_dp]
+    lib.dragg_mpc_ev_reset.argtypes = [ctypes.POINTER(Dims), ctypes.POINTER(Ev), c_dp, c_dp]
     if lib.dragg_mpc_abi_version() != ABI_VERSION:
         raise DraggError("ABI version mismatch between dragg_amd and libdragg_mi355x.so")
     if not os.environ.get("DRAGG_LIB"):

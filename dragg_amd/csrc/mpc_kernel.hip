@@ -5353,6 +5353,27 @@ __global__ __launch_bounds__(REP_NT) void env_reset_kernel(EnvArgs a) {
     if (blockIdx.x == 0 && threadIdx.x == 0) env_setpoint(a, g, 0, a.start_load, a.start_load, 0.0, true);
 }
 
+// dragg_mpc_ev_reset: env_reset_kernel's fill over a fleet's segments alone (no environment state beside them)
+struct EvResetArgs {
+    Segs segs;
+    const unsigned char* mask;
+};
+__global__ __launch_bounds__(REP_NT) void ev_reset_kernel(EvResetArgs a) {
+    const int g = (int)blockIdx.y;
+    if (!__builtin_amdgcn_readfirstlane((int)a.mask[g])) return;
+    seg_walk(a.segs, [&](const Seg& s, long long r, long long i, auto unit) {
+        using T = decltype(unit);
+        T v;
+        if constexpr (sizeof(T) == 16) {
+            const unsigned lo = (unsigned)s.fill, hi = (unsigned)(s.fill >> 32);
+            v = uint4{lo, hi, lo, hi};
+        } else {
+            v = (T)s.fill;
+        }
+        *seg_at<T>(s.dst, r * s.dst_stride + g * s.group_bytes, i) = v;
+    });
+}
+
 // dragg_mpc_select_paths: the choice over K-step rollouts.  Block e (one wave) owns episode e, a lane one of its
 // candidates, 64 at a time in ascending c: the lane walks its candidate's K loads, rebuilding for step j the
 // window gen_setpoint would hold after j plays -- element i of it is tracked[i + n] while that exists, then the
@@ -5612,6 +5633,13 @@ struct EvArgs {
     const double *tou, *reward_price;
     int start_index, t, G;
 };
+// dragg_mpc_ev_step_episodes: the groups' own clocks and start indices and the class map beside the step's arguments
+// (a struct of its own: the kernels of the other two entries keep their arguments)
+struct EvEpArgs : EvArgs {
+    dragg_mpc_episodes ep;
+    const int32_t* price_class;     // [Mb] by base vehicle (n_classes > 1), else unused
+    int n_classes;
+};
 
 DEV EvLds ev_carve(double* s, int H) {
     const int cap = seg_cap(H);
@@ -5682,17 +5710,46 @@ DEV double ev_objective(const EvLds& L, int H) {
     return s;
 }
 
-// STEP: the stage arrays from the vehicle's parameters, the clock and the price (dragg_mpc_ev_step); else the
-// explicit ones.  Everything after the prologue is one code path.
-template <bool STEP>
-__global__ __launch_bounds__(EV_NT) void ev_kernel(EvArgs a) {
+// The mode of the vehicle kernel's prologue.  EVM_STEP: the stage arrays from the vehicle's parameters, the clock
+// and the price (dragg_mpc_ev_step); EVM_EXPLICIT: the explicit ones; EVM_EPISODES: EVM_STEP with the group's own
+// clock, start index, day clock and (class's) price row (dragg_mpc_ev_step_episodes).  Everything after the
+// prologue is one code path.
+constexpr int EVM_EXPLICIT = 0, EVM_STEP = 1, EVM_EPISODES = 2;
+
+// the step of day of stage 0: (day_offset + (start - start0) + t) mod D as the non-negative remainder, every term
+// reduced into [0, D) first so that no sum leaves 32 bits (t >= 0, 0 <= day_offset < D)
+DEV int ev_day_step(int day_offset, int start0, int start, int t, int D) {
+    int ds = start % D, d0 = start0 % D;
+    if (ds < 0) ds += D;
+    if (d0 < 0) d0 += D;
+    return (day_offset + ds + (D - d0) + t % D) % D;
+}
+
+template <int MODE, class Args>
+DEV void ev_body(const Args& a) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr bool STEP = MODE != EVM_EXPLICIT;
     const int wid = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
     const int M = a.ev.n_vehicles;
     const int r = __builtin_amdgcn_readfirstlane((int)blockIdx.x * EV_WAVES + wid);
     if (r >= M) return;
     const int H = a.d.horizon;
+    // an episode step: the group's keys, wave-uniform (r is), read once through scalar loads.  An idle group --
+    // a negative clock, or a window that leaves the environment lists (group_idle's rule, so that an episode's
+    // homes and vehicles idle together) -- leaves here, before any access to its arrays
+    int ep_t = 0, ep_start = 0, ep_row = 0;
+    if constexpr (MODE == EVM_EPISODES) {
+        const unsigned Mb = (unsigned)M / (unsigned)a.G;
+        const unsigned g = (unsigned)r / Mb, v = (unsigned)r - g * Mb;
+        ep_t = a.ep.timestep ? a.ep.timestep[g] : a.t;
+        ep_start = a.ep.start_index ? a.ep.start_index[g] : a.start_index;
+        if (ep_t < 0 || ep_start < 0 || (long long)ep_start + ep_t + H >= (long long)a.d.n_env) return;
+        ep_row = (int)g;
+        if (a.n_classes > 1)         // the class is clamped: no device data can point past the price rows
+            ep_row = (int)g * a.n_classes +
+                     __builtin_amdgcn_readfirstlane(min(max(a.price_class[v], 0), a.n_classes - 1));
+    }
     const EvLds L = ev_carve(smem + (size_t)wid * ev_lds_doubles(H), H);
     const double* P = a.ev.params;
     EvCar c;
@@ -5709,10 +5766,13 @@ __global__ __launch_bounds__(EV_NT) void ev_kernel(EvArgs a) {
         const double drain = trips ? P[(size_t)DRAGG_EVP_TRIP * M + r] / (double)(ret - dep) : 0.0;
         const double lo_dep = fmax(Emin, P[(size_t)DRAGG_EVP_EREQ * M + r]);
         const int D = 24 * c.dt;
-        const int c0 = (a.ev.day_offset + a.t) % D;
-        const int s0 = a.start_index + a.t;
+        const int t = MODE == EVM_EPISODES ? ep_t : a.t;
+        const int c0 = MODE == EVM_EPISODES ? ev_day_step(a.ev.day_offset, a.start_index, ep_start, t, D)
+                                            : (a.ev.day_offset + t) % D;
+        const int s0 = (MODE == EVM_EPISODES ? ep_start : a.start_index) + t;
         const int n_rp = a.d.n_rp;
-        const double* rpl = a.reward_price + (size_t)((unsigned)r / ((unsigned)M / (unsigned)a.G)) * n_rp;
+        const double* rpl = a.reward_price + (size_t)(MODE == EVM_EPISODES ? (unsigned)ep_row
+                                                      : (unsigned)r / ((unsigned)M / (unsigned)a.G)) * n_rp;
         for (int k = lane; k < H; k += WAVE) {
             const int sk = (c0 + k) % D, sn = (c0 + k + 1) % D;
             const bool away = trips && dep <= sk && sk < ret;
@@ -5725,7 +5785,7 @@ __global__ __launch_bounds__(EV_NT) void ev_kernel(EvArgs a) {
             L.lo[k] = trips && sn == dep ? lo_dep : Emin;
             L.hi[k] = c.Emax;
         }
-        c.E0 = a.t == 0 ? P[(size_t)DRAGG_EVP_EINIT * M + r] : a.ev.vals[(size_t)DRAGG_EVK_E * M + r];
+        c.E0 = t == 0 ? P[(size_t)DRAGG_EVP_EINIT * M + r] : a.ev.vals[(size_t)DRAGG_EVK_E * M + r];
     } else {
         for (int k = lane; k < H; k += WAVE) {
             const size_t i = (size_t)k * M + r;
@@ -5769,9 +5829,17 @@ __global__ __launch_bounds__(EV_NT) void ev_kernel(EvArgs a) {
         a.ev.obj[r] = obj;
     }
 }
+template <bool STEP>
+__global__ __launch_bounds__(EV_NT) void ev_kernel(EvArgs a) {
+    ev_body<STEP ? EVM_STEP : EVM_EXPLICIT>(a);
+}
+__global__ __launch_bounds__(EV_NT) void ev_episode_kernel(EvEpArgs a) { ev_body<EVM_EPISODES>(a); }
 
-// dragg_mpc_ev_aggregate: block g sums group g's Mb vehicles (the header's order)
-__global__ __launch_bounds__(AGG_NT) void ev_aggregate_kernel(const double* vals, int M, int Mb, double* out) {
+// dragg_mpc_ev_aggregate: block g sums group g's Mb vehicles (the header's order).  ONTO
+// (dragg_mpc_ev_aggregate_onto): the same sums s in the same order, then out = base + s as one plain add (base
+// is read before out is written: they may be the same array) and s itself to ev_out where that is given
+template <bool ONTO>
+DEV void ev_aggregate_body(const double* vals, int M, int Mb, const double* base, double* out, double* ev_out) {
 #pragma clang fp contract(off)
     __shared__ double red[3][AGG_NT / WAVE];
     const size_t off = (size_t)blockIdx.x * Mb;
@@ -5797,8 +5865,21 @@ __global__ __launch_bounds__(AGG_NT) void ev_aggregate_kernel(const double* vals
         for (int width = AGG_NT / WAVE / 2; width >= 1; width /= 2)
 #pragma unroll
             for (int m = 0; m < width; ++m) t[m] = t[2 * m] + t[2 * m + 1];
-        out[(size_t)blockIdx.x * 3 + threadIdx.x] = t[0];
+        const size_t j = (size_t)blockIdx.x * 3 + threadIdx.x;
+        if (ONTO) {
+            out[j] = base[j] + t[0];
+            if (ev_out) ev_out[j] = t[0];
+        } else {
+            out[j] = t[0];
+        }
     }
+}
+__global__ __launch_bounds__(AGG_NT) void ev_aggregate_kernel(const double* vals, int M, int Mb, double* out) {
+    ev_aggregate_body<false>(vals, M, Mb, nullptr, out, nullptr);
+}
+__global__ __launch_bounds__(AGG_NT) void ev_aggregate_onto_kernel(const double* vals, int M, int Mb,
+                                                                   const double* base, double* out, double* ev_out) {
+    ev_aggregate_body<true>(vals, M, Mb, base, out, ev_out);
 }
 
 // --------------------------------------------------------------------------------------
@@ -6114,16 +6195,19 @@ int ev_args(const dragg_mpc_dims* dims, const dragg_mpc_ev* ev, EvArgs* a) {
     a->G = G;
     return DRAGG_OK;
 }
-template <bool STEP>
-int ev_launch(const EvArgs& a, hipStream_t s) {
+template <class Args>
+int ev_launch_kernel(const void* kern, const Args& a, hipStream_t s) {
     int dev;
     if (int rc = current_device(&dev)) return rc;
-    const void* kern = reinterpret_cast<const void*>(&ev_kernel<STEP>);
     if (!raise_lds_limit(dev, kern)) return DRAGG_E_LDS;
     const int blocks = (a.ev.n_vehicles + EV_WAVES - 1) / EV_WAVES;
-    void* args[] = {const_cast<EvArgs*>(&a)};
+    void* args[] = {const_cast<Args*>(&a)};
     (void)hipLaunchKernel(kern, dim3(blocks), dim3(EV_NT), args, ev_block_lds(a.d.horizon), s);
     return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+}
+template <bool STEP>
+int ev_launch(const EvArgs& a, hipStream_t s) {
+    return ev_launch_kernel(reinterpret_cast<const void*>(&ev_kernel<STEP>), a, s);
 }
 
 }  // namespace
@@ -6648,6 +6732,102 @@ int dragg_mpc_ev_aggregate(const dragg_mpc_dims* dims, const dragg_mpc_ev* ev, d
     hipLaunchKernelGGL(ev_aggregate_kernel, dim3(a.G), dim3(AGG_NT), 0, (hipStream_t)stream, ev->vals, ev->n_vehicles,
                        ev->n_vehicles / a.G, out);
     return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+}
+
+// The episode step: dragg_mpc_ev_step's checks, the shared start index and timestep against the lists only where a
+// group can read them (dragg_mpc_step_episodes' rule: the groups' own values are checked on the device)
+int dragg_mpc_ev_step_episodes(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob, const dragg_mpc_episodes* ep,
+                               const dragg_mpc_classes* classes, const dragg_mpc_ev* ev, int32_t timestep,
+                               void* stream) {
+    EvEpArgs a{};
+    const int rc = ev_args(dims, ev, &a);
+    if (rc) return rc;
+    const int cls = classes_in_effect(classes);
+    if (!ep || !prob || cls < 0 || (!ep->timestep && timestep < 0)) return DRAGG_E_ARG;
+    if (ev->n_vehicles == 0) return DRAGG_OK;
+    if (!ev_state_ok(ev) || !prob->tou || !prob->reward_price) return DRAGG_E_ARG;
+    if (dims->n_rp != 1 && dims->n_rp < dims->horizon) return DRAGG_E_ARG;
+    if (!ep->start_index &&
+        (prob->start_index < 0 || (long long)prob->start_index + (ep->timestep ? 0 : timestep) + dims->horizon >=
+                                      (long long)dims->n_env))
+        return DRAGG_E_ARG;
+    a.tou = prob->tou;
+    a.reward_price = prob->reward_price;
+    a.start_index = prob->start_index;
+    a.t = timestep;
+    a.ep = *ep;
+    a.price_class = cls ? classes->price_class : nullptr;
+    a.n_classes = cls ? classes->n_classes : 1;
+    return ev_launch_kernel(reinterpret_cast<const void*>(&ev_episode_kernel), a, (hipStream_t)stream);
+}
+
+int dragg_mpc_ev_aggregate_onto(const dragg_mpc_dims* dims, const dragg_mpc_ev* ev, const double* base, double* out,
+                                double* ev_out, void* stream) {
+    EvArgs a;
+    const int rc = ev_args(dims, ev, &a);
+    if (rc) return rc;
+    if (!base || !out || (ev->n_vehicles > 0 && !ev->vals)) return DRAGG_E_ARG;
+    if (ev->n_vehicles == 0) {          // out = base to the bit (base + 0.0 would turn a -0.0 over)
+        const size_t bytes = (size_t)a.G * 3 * sizeof(double);
+        if (out != base && hipMemcpyAsync(out, base, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+            return DRAGG_E_HIP;
+        if (ev_out && hipMemsetAsync(ev_out, 0, bytes, (hipStream_t)stream) != hipSuccess) return DRAGG_E_HIP;
+        return DRAGG_OK;
+    }
+    hipLaunchKernelGGL(ev_aggregate_onto_kernel, dim3(a.G), dim3(AGG_NT), 0, (hipStream_t)stream, ev->vals,
+                       ev->n_vehicles, ev->n_vehicles / a.G, base, out, ev_out);
+    return hipGetLastError() == hipSuccess ? DRAGG_OK : DRAGG_E_HIP;
+}
+
+// the fleet's twins of dragg_mpc_adopt and dragg_mpc_env_reset: the same mover over a fleet's four arrays
+int dragg_mpc_ev_adopt(const dragg_mpc_dims* dst_dims, int32_t copies, const int32_t* choice,
+                       const dragg_mpc_ev* src_ev, const dragg_mpc_ev* dst_ev, void* stream) {
+    if (!dst_dims || dst_dims->horizon < 1 || copies < 1 || !choice || !src_ev || !dst_ev || dst_ev->n_vehicles < 0)
+        return DRAGG_E_ARG;
+    const int E = max(dst_dims->n_groups, 1);
+    const long long Md = dst_ev->n_vehicles;
+    if (dst_dims->n_groups < 0 || E > 65535 || Md % E != 0 || (long long)src_ev->n_vehicles != copies * Md)
+        return DRAGG_E_ARG;
+    if (Md == 0) return DRAGG_OK;
+    if (!src_ev->vals || !src_ev->fc || !src_ev->status || !src_ev->obj || !dst_ev->vals || !dst_ev->fc ||
+        !dst_ev->status || !dst_ev->obj)
+        return DRAGG_E_ARG;
+    const long long Mb = Md / E;
+    AdoptArgs a{};
+    a.copies = copies;
+    a.E = E;
+    a.choice = choice;
+    bool ok = true;
+    auto seg = [&](const void* s, void* d, long long col, int rows, long long elem) {
+        ok = seg_add(a.segs, s, d, copies * Md * col, Md * col, Mb * col, rows, elem) && ok;
+    };
+    seg(src_ev->fc, dst_ev->fc, (long long)DRAGG_NEVK * dst_dims->horizon * 8, 1, 8);
+    seg(src_ev->vals, dst_ev->vals, 8, DRAGG_NEVV, 8);
+    seg(src_ev->obj, dst_ev->obj, 8, 1, 8);
+    seg(src_ev->status, dst_ev->status, 4, 1, 4);
+    return ok ? seg_launch(adopt_kernel, a, E, stream) : DRAGG_E_ARG;
+}
+
+int dragg_mpc_ev_reset(const dragg_mpc_dims* dims, const dragg_mpc_ev* ev, const uint8_t* mask, void* stream) {
+    if (!dims || dims->horizon < 1 || !ev || ev->n_vehicles < 0 || !mask) return DRAGG_E_ARG;
+    const int G = max(dims->n_groups, 1);
+    const long long M = ev->n_vehicles;
+    if (dims->n_groups < 0 || G > 65535 || M % G != 0) return DRAGG_E_ARG;
+    if (M == 0) return DRAGG_OK;
+    if (!ev->vals || !ev->fc || !ev->status || !ev->obj) return DRAGG_E_ARG;
+    const long long Mb = M / G;
+    const unsigned long long nan = 0x7FF8000000000000ull;
+    EvResetArgs a{};
+    a.mask = mask;
+    bool ok = true;
+    auto seg = [&](void* d, long long col, int rows, long long elem, unsigned long long fill) {
+        ok = seg_add(a.segs, nullptr, d, M * col, M * col, Mb * col, rows, elem, fill) && ok;
+    };
+    seg(ev->fc, (long long)DRAGG_NEVK * dims->horizon * 8, 1, 8, nan);
+    seg(ev->vals, 8, DRAGG_NEVV, 8, nan);
+    seg(ev->obj, 8, 1, 8, nan);
+    seg(ev->status, 4, 1, 4, 0);
+    return ok ? seg_launch(ev_reset_kernel, a, G, stream) : DRAGG_E_ARG;
 }
 
 }  // extern "C"

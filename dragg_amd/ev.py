@@ -71,6 +71,17 @@ def ev_schedule(P, dt, day_offset, t, H):
     return {"rate_ch": rate_ch, "rate_dis": rate_dis, "drain": drain, "lo": lo, "hi": hi, "away": away}
 
 
+def ev_episode_day_step(day_offset, start0, start, t, dt):
+    """The step of day of stage 0 of an episode step (dragg_mpc_ev_step_episodes' day clock): `day_offset` is the
+    step of day of environment index `start0`, the episode starts at index `start` and stands at timestep `t`
+    -> (day_offset + (start - start0) + t) mod 24 dt, the non-negative remainder.  Scalars or integer arrays."""
+    D = 24 * int(dt)
+    d = (np.asarray(day_offset, dtype=np.int64) + (np.asarray(start, dtype=np.int64) - np.asarray(start0, dtype=np.int64))
+         + np.asarray(t, dtype=np.int64))
+    r = np.mod(d, D)
+    return int(r) if r.ndim == 0 else r
+
+
 def ev_fallback(P, dt, rate_ch, drain, E0):
     """The uncontrolled rule of a vehicle without a trajectory, in the kernel's operation order (one column per
     vehicle): -> (ch [H][M], E [H][M]); dis is zero."""
@@ -105,8 +116,10 @@ class EVFleet:
 
     tou, start_index : the environment's TOU list and start index (the homes' own).
     reward_price : as MPCBatch's (length 1 or >= H; a grouped fleet: [G][n] or one list for every group).
-    day_offset : the step of day of timestep 0.
-    groups : G > 1: G consecutive replicas of the vehicles, replica g under price row g (`replicate_from`).
+    day_offset : the step of day of timestep 0, i.e. of environment index `start_index`.
+    groups : G > 1: G consecutive replicas of the vehicles, replica g under price row g (`replicate_from`).  The
+        groups may be episodes, each with its own start index and clock (`step_episodes`), and the vehicles may
+        have price classes (`set_price_classes`): the vector environments' fleet.
     rank, world : keep the vehicles of homes rank, rank + world, ... only (the homes' `shard_index`).
     template_home : a home of the community, for the dims of a fleet without vehicles (its steps are no-ops).
     """
@@ -148,6 +161,7 @@ class EVFleet:
         if rc < 0:
             L.check(rc)
         self.lds_bytes = rc
+        self.n_classes, self.price_class, self.price_class_host = 1, None, None
         self.set_environment(tou if tou is not None else [0.0], start_index)
         self.set_reward_price(reward_price)
         self.vals = torch.full((L.NEVV, self.M), float("nan"), dtype=torch.float64, device=dev)
@@ -165,11 +179,34 @@ class EVFleet:
         self.start_index = int(start_index)
         self.dims.n_env = int(self.tou.numel())
 
+    def set_price_classes(self, vehicle_classes, n_classes=None):
+        """The vehicles' price classes: `vehicle_classes`, a host int sequence [Mb] by base vehicle (each vehicle's
+        owner home's class), P = `n_classes` (None: the largest class + 1), shared by every group.  The fleet then
+        holds P price rows per group and `step_episodes` solves vehicle v of group g under row (g, class of v).
+        The rows start over at price 0.  `_lib.price_class_map`'s checks; P == 1 (or None): no classes."""
+        import torch
+        if vehicle_classes is None:
+            cm, P = None, 1
+        else:
+            cm, P = L.price_class_map(vehicle_classes, self.Mb, n_classes)
+        self.n_classes = P
+        self.price_class_host = cm if P > 1 else None
+        self.price_class = torch.tensor(cm, dtype=torch.int32, device=self.device).contiguous() if P > 1 else None
+        self.set_reward_price(torch.zeros((self.groups, P) if P > 1 else (self.groups, 1), dtype=torch.float64))
+
     def set_reward_price(self, rp):
-        """As MPCBatch.set_reward_price without price classes: one list, or [G][n] for a grouped fleet."""
+        """As MPCBatch.set_reward_price: one list, or [G][n] for a grouped fleet; with P price classes
+        (`set_price_classes`) [G][P][n], or [G][P] (class scalars)."""
         rp = L.device_f64(rp if hasattr(rp, "shape") else [float(v) for v in rp], self.device)
-        G = self.groups
-        if G > 1:
+        G, P = self.groups, self.n_classes
+        if P > 1:
+            if tuple(rp.shape) == (G, P):
+                rp = rp.reshape(G, P, 1)
+            if rp.dim() != 3 or tuple(rp.shape[:2]) != (G, P) or rp.shape[2] < 1:
+                raise ValueError(f"a fleet of {G} groups and {P} price classes takes reward prices [{G}][{P}] or "
+                                 f"[{G}][{P}][n], not {list(rp.shape)}")
+            n = int(rp.shape[2])
+        elif G > 1:
             if rp.dim() < 2:
                 rp = rp.reshape(1, -1).expand(G, -1)
             if rp.dim() != 2 or rp.shape[0] != G:
@@ -197,6 +234,24 @@ class EVFleet:
         L.check(self.lib.dragg_mpc_ev_step(self.dims, self._problem(), self._ev(), int(t),
                                            L.stream_ptr(stream, self.device)))
 
+    def step_episodes(self, starts, clocks, stream=None, t=0):
+        """One step of a fleet whose groups are episodes (dragg_mpc_ev_step_episodes): group g at its own start
+        index `starts[g]` and timestep `clocks[g]` (contiguous device int32 [G]; a negative clock, or a window that
+        leaves the environment lists: the group is idle and no byte of it is written), under its own price row --
+        its vehicles' classes' rows with price classes.  None for either: the fleet's own start_index / `t` for
+        every group.  The day clock follows the start index (`ev_episode_day_step`).  No synchronisation."""
+        import torch
+        for name, x in (("starts", starts), ("clocks", clocks)):
+            if x is not None and (not torch.is_tensor(x) or x.device != self.device or x.dtype != torch.int32
+                                  or tuple(x.shape) != (self.groups,) or not x.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous device tensor [{self.groups}] of {torch.int32}, not "
+                                 f"{getattr(x, 'dtype', type(x))} {list(getattr(x, 'shape', []))}")
+        ep = L.Episodes(seed=None, start_index=L.ptr(starts), timestep=L.ptr(clocks))
+        cls = L.Classes(n_classes=int(self.n_classes), price_class=L.ptr(self.price_class))
+        L.check(self.lib.dragg_mpc_ev_step_episodes(self.dims, self._problem(), ep, cls, self._ev(), int(t),
+                                                    L.stream_ptr(stream, self.device)))
+        self._keep = (starts, clocks)           # (the launch is asynchronous: keep its keys alive)
+
     def solve_explicit(self, price, rate_ch, rate_dis, drain, lo, hi, E0, stream=None):
         """The general storage LP on explicit per-stage inputs [H][M] and E0 [M] (dragg_mpc_ev_solve_explicit):
         writes vals, fc, status, obj."""
@@ -222,7 +277,50 @@ class EVFleet:
         s = self.aggregate_groups(out.reshape(self.groups, 3) if out is not None else None, stream)
         return s.reshape(3) if self.groups == 1 else s
 
+    def aggregate_onto(self, base, out=None, stream=None):
+        """`base` ([G][3], the homes' sums) plus the vehicles' (dragg_mpc_ev_aggregate_onto): `aggregate_groups`'
+        rows in the same summation order, then one fp64 add per entry -> `out` (default: `base` itself, in place).
+        The vehicles' own rows go to `self.sums`."""
+        import torch
+        out = base if out is None else out
+        for name, x in (("base", base), ("out", out)):
+            if not torch.is_tensor(x) or x.device != self.device or x.dtype != torch.float64 \
+                    or x.numel() != self.groups * 3 or not x.is_contiguous():
+                raise ValueError(f"aggregate_onto: {name} must be a contiguous device float64 tensor [{self.groups}][3]")
+        L.check(self.lib.dragg_mpc_ev_aggregate_onto(self.dims, self._ev(), L.ptr(base), L.ptr(out), L.ptr(self.sums),
+                                                     L.stream_ptr(stream, self.device)))
+        return out
+
     # ------------------------------------------------------------------ state
+    def adopt_from(self, src, choice, stream=None):
+        """`MPCBatch.adopt_from` for a fleet (dragg_mpc_ev_adopt): `src` holds C copies of this fleet's E groups,
+        copy-major; group e takes the vals columns, fc blocks, status and obj of copy `choice[e]` (contiguous
+        device int32 [E]), bit for bit; an entry outside [0, C) leaves its group untouched.  `src`: an EVFleet,
+        or anything with its arrays (vals, fc_store, status, obj, M, H)."""
+        import torch
+        copies = src.M // self.M if self.M else 1
+        if copies < 1 or src.M != copies * self.M or src.H != self.H:
+            raise ValueError(f"adopt_from: a fleet of {self.M} vehicles (H = {self.H}) cannot adopt from {src.M} "
+                             f"vehicles (H = {src.H}): the source holds whole copies of it")
+        if not torch.is_tensor(choice) or choice.device != self.device or choice.dtype != torch.int32 \
+                or tuple(choice.shape) != (self.groups,) or not choice.is_contiguous():
+            raise ValueError(f"choice must be a contiguous device tensor [{self.groups}] of {torch.int32}")
+        s = L.Ev(params=None, vals=L.ptr(src.vals), fc=L.ptr(src.fc_store), status=L.ptr(src.status),
+                 obj=L.ptr(src.obj), day_offset=self.day_offset, n_vehicles=src.M)
+        L.check(self.lib.dragg_mpc_ev_adopt(self.dims, copies, L.ptr(choice), s, self._ev(),
+                                            L.stream_ptr(stream, self.device)))
+        self._keep = (src, choice)
+
+    def reset_groups(self, mask, stream=None):
+        """Start the masked groups (`mask`: contiguous device bool [G]) over (dragg_mpc_ev_reset): their vals
+        columns, fc blocks and obj NaN, their status 0 -- the state of a new fleet; the others keep every byte."""
+        import torch
+        if not torch.is_tensor(mask) or mask.device != self.device or mask.dtype != torch.bool \
+                or tuple(mask.shape) != (self.groups,) or not mask.is_contiguous():
+            raise ValueError(f"mask must be a contiguous device bool tensor [{self.groups}]")
+        L.check(self.lib.dragg_mpc_ev_reset(self.dims, self._ev(), L.ptr(mask), L.stream_ptr(stream, self.device)))
+        self._keep = (mask,)
+
     def snapshot(self):
         return self.vals.clone(), self.fc_store.clone(), self.status.clone(), self.obj.clone()
 
@@ -231,20 +329,26 @@ class EVFleet:
             dst.copy_(src)
 
     def replicate_from(self, base):
-        """A grouped fleet's state: every group a copy of `base`'s (a fleet of the same vehicles, one group)."""
-        if base.M != self.Mb or base.H != self.H:
-            raise ValueError(f"replicate_from: a base fleet of {self.Mb} vehicles at H = {self.H}, "
-                             f"not {base.M} at H = {base.H}")
-        G = self.groups
-        self.vals.view(L.NEVV, G, self.Mb).copy_(base.vals.unsqueeze(1).expand(-1, G, -1))
-        self.fc_store.view(G, self.Mb, L.NEVK, self.H).copy_(base.fc_store.unsqueeze(0).expand(G, -1, -1, -1))
-        self.status.view(G, self.Mb).copy_(base.status.unsqueeze(0).expand(G, -1))
-        self.obj.view(G, self.Mb).copy_(base.obj.unsqueeze(0).expand(G, -1))
+        """A grouped fleet's state: every group a copy of `base`'s (a fleet of the same vehicles, one group).
+        `base` may itself be a grouped fleet of E groups: this fleet (C * E groups) then holds C copies of it,
+        copy-major -- copy c of base group e is group c * E + e (as `MPCBatch.replicate_from`)."""
+        E = max(getattr(base, "groups", 1), 1)
+        C = self.groups // E
+        if C < 1 or C * E != self.groups or base.M != E * self.Mb or base.H != self.H:
+            raise ValueError(f"replicate_from: a base fleet of {self.Mb} vehicles at H = {self.H} (in groups that "
+                             f"divide {self.groups}), not {base.M} at H = {base.H} in {E} groups")
+        self.vals.view(L.NEVV, C, base.M).copy_(base.vals.unsqueeze(1).expand(-1, C, -1))
+        self.fc_store.view(C, base.M, L.NEVK, self.H).copy_(base.fc_store.unsqueeze(0).expand(C, -1, -1, -1))
+        self.status.view(C, base.M).copy_(base.status.unsqueeze(0).expand(C, -1))
+        self.obj.view(C, base.M).copy_(base.obj.unsqueeze(0).expand(C, -1))
 
-    def schedule(self, t):
-        """`ev_schedule` of this fleet's vehicles (tiled over the groups) at timestep t."""
+    def schedule(self, t, start=None):
+        """`ev_schedule` of this fleet's vehicles (tiled over the groups) at timestep t; `start`: of an episode
+        that starts at that environment index (the day clock of `ev_episode_day_step`; default: the fleet's own)."""
         P = np.tile(self.params_host, (1, self.groups)) if self.groups > 1 else self.params_host
-        return ev_schedule(P, self.dt, self.day_offset, t, self.H)
+        day = (self.day_offset if start is None
+               else ev_episode_day_step(self.day_offset, self.start_index, int(start), 0, self.dt))
+        return ev_schedule(P, self.dt, day, t, self.H)
 
 
 def build_fleet(homes, **kw):

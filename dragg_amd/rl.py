@@ -200,7 +200,9 @@ class VectorEnv:
         # [E][C][P] or [E][C][P][n]
         self.n_classes, self.class_names = getattr(va, "n_classes", 1), getattr(va, "class_names", None)
         self.prev_timesteps = config["agg"]["rl"]["prev_timesteps"]
-        self.max_poss_load = (sum(I.max_load(h) for h in va.homes) if max_poss_load is None else max_poss_load)
+        # (an aggregator with vehicles: each vehicle's max_rate on top of the homes' own loads)
+        self.max_poss_load = (sum(I.max_load(h) for h in va.homes) + getattr(va, "vehicle_max_rate", 0.0)
+                              if max_poss_load is None else max_poss_load)
         self.n_homes = va.Nb if n_homes is None else int(n_homes)
         self.timestep = np.zeros(self.E, dtype=np.int64)
         self.parked = np.zeros(self.E, dtype=bool)
@@ -345,7 +347,9 @@ class DeviceVectorEnv:
         self.E, self.T = va.E, va.num_timesteps
         self.n_classes, self.class_names = getattr(va, "n_classes", 1), getattr(va, "class_names", None)
         self.prev_timesteps = config["agg"]["rl"]["prev_timesteps"]
-        self.max_poss_load = (sum(I.max_load(h) for h in va.homes) if max_poss_load is None else max_poss_load)
+        # (an aggregator with vehicles: each vehicle's max_rate on top of the homes' own loads)
+        self.max_poss_load = (sum(I.max_load(h) for h in va.homes) + getattr(va, "vehicle_max_rate", 0.0)
+                              if max_poss_load is None else max_poss_load)
         self.n_homes = va.Nb if n_homes is None else int(n_homes)
         self.state = va.env_state(self.prev_timesteps, self.max_poss_load, 3 * self.n_homes)
         self.choice = self.scores = None

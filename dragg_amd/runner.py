@@ -260,7 +260,7 @@ class Aggregator:
         return self.avg_load
 
     def rl_vector(self, episodes, seeds=None, start_indices=None, device_env=False, plan_keys=(), plan_rows=(),
-                  price_classes=None):
+                  price_classes=None, vehicles=None):
         """A vector environment of `episodes` independent runs of the loaded community (`get_homes`), all
         stepped as one grouped batch (dragg_amd.vector.VectorAggregator, rl.VectorEnv): default seeds
         `simulation.random_seed + e`, default start indices the config's own.  device_env=True: an
@@ -269,14 +269,21 @@ class Aggregator:
         homes -- "type" (class = home type: base 0, pv_only 1, battery_only 2, pv_battery 3; P = 4 even if a type is
         absent) or an int sequence, one class per loaded home in `all_homes`' order (default: the config's
         `rl.utility.price_classes`, else none); actions and candidates then take the class shapes of
-        `VectorAggregator`.  One rank only."""
+        `VectorAggregator`.  `vehicles`: a config with a `[home.ev]` share > 0 must choose -- True: the vehicles
+        `run()` would build (the same sections, the day clock re-based to environment index 0) are stepped beside
+        every episode's homes (`VectorAggregator(vehicles=True)`) and count in the sums and in max_poss_load;
+        False: they are left out on purpose; None (default) raises NotImplementedError for such a config rather
+        than deciding silently.  One rank only."""
         from .rl import DeviceVectorEnv, VectorEnv
         from .vector import VectorAggregator
         if self.world > 1:
             raise ValueError("rl_vector runs on one rank: episodes are not sharded over ranks")
-        if float(((self.config.get("home") or {}).get("ev") or {}).get("share", 0.0)) > 0.0:
-            raise NotImplementedError("rl_vector: the vector environments do not take an EV fleet yet; this config's "
-                                      "[home.ev] section is served by run() and run_rl_agg only")
+        ev_cfg = (self.config.get("home") or {}).get("ev") or {}
+        ev_share = float(ev_cfg.get("share", 0.0))
+        if ev_share > 0.0 and vehicles is None:
+            raise NotImplementedError("rl_vector: this config's [home.ev] section asks for an EV fleet; choose "
+                                      "vehicles=True (the vehicles are stepped beside every episode's homes) or "
+                                      "vehicles=False (they are left out)")
         if not hasattr(self, "start_hour_index"):
             self.flush()
         E = int(episodes)
@@ -291,13 +298,22 @@ class Aggregator:
             pc, n_classes = price_class_map(list(price_classes), len(self.all_homes))
             price_classes = [int(c) for c, h in zip(pc, self.all_homes)
                              if self.check_type == "all" or h["type"] == self.check_type]
+        ev_kw, ev_rate = {}, 0.0
+        if vehicles and ev_share > 0.0:
+            from .community import ev_sections
+            secs = ev_sections(len(checked), ev_cfg["share"], self.dt, seed, ev_cfg)
+            checked = [dict(h, ev=secs[i]) if i in secs else h for i, h in enumerate(checked)]
+            # _fleet's day clock is that of environment index start_hour_index: re-based to index 0
+            day0 = (self.start_dt.hour * self.dt + self.start_dt.minute // self.dt_interval) % (24 * self.dt)
+            ev_kw = dict(vehicles=True, day_offset=(day0 - self.start_hour_index) % (24 * self.dt))
+            ev_rate = sum(float(s["max_rate"]) for s in secs.values())
         va = VectorAggregator(checked, oat, ghi, tou, E,
                               [seed + e for e in range(E)] if seeds is None else seeds,
                               [self.start_hour_index] * E if start_indices is None else start_indices,
                               self.num_timesteps, int_mode=self.int_mode, device=self.device,
-                              price_classes=price_classes, n_classes=n_classes,
+                              price_classes=price_classes, n_classes=n_classes, **ev_kw,
                               **({"batch_cls": self.batch_cls} if self.batch_cls else {}))
-        kw = dict(max_poss_load=sum(I.max_load(h) for h in self.all_homes), n_homes=len(self.all_homes))
+        kw = dict(max_poss_load=sum(I.max_load(h) for h in self.all_homes) + ev_rate, n_homes=len(self.all_homes))
         if not device_env:
             if plan_keys or plan_rows:
                 raise ValueError("plan observations need device_env=True (rl.DeviceVectorEnv)")

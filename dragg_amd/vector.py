@@ -32,12 +32,19 @@ price per class ([E][P]), every home reads its class's row (dragg_mpc_step_class
 reduces the plans per (episode, class) (dragg_mpc_plan_classes; `plan_classes_reference` restates it).  The
 class-c homes of an episode equal, bit for bit, the same homes of a single run under class c's prices alone.
 
+`VectorAggregator(..., vehicles=True)` steps the homes' electric vehicles beside them: an E-group `EVFleet` of its
+own whose groups follow the episodes' start indices, clocks, resets, price rows and price classes
+(dragg_mpc_ev_step_episodes), its three sums added onto the homes' before anything is filed, swept and adopted with
+the homes.  The homes never see the fleet: their rows are those of the same aggregator
+without vehicles, and every episode's sums and fleet state are a single `DeviceAggregator(ev=...)` run's, bit for bit.
+
 One rank only: sharding episodes over ranks is not built.
 """
 import numpy as np
 import torch
 
 from . import _lib as L
+from .ev import EVFleet
 from .mpc import MPCBatch
 
 
@@ -292,18 +299,40 @@ class HeldReplicas:
         self.hist_row = getattr(rb, "hist_row", None)
 
 
+class HeldFleet:
+    """`HeldReplicas` for the replica fleet: the arrays `EVFleet.adopt_from` reads, allocated once."""
+    KEYS = ("vals", "fc_store", "status", "obj")
+
+    def __init__(self, rf):
+        self.M, self.H, self.groups = rf.M, rf.H, rf.groups
+        for k in self.KEYS:
+            setattr(self, k, torch.empty_like(getattr(rf, k)))
+
+    def fill(self, rf):
+        for k in self.KEYS:
+            getattr(self, k).copy_(getattr(rf, k))
+
+
 class VectorAggregator:
     def __init__(self, homes, oat, ghi, tou, episodes, seeds, start_indices, num_timesteps, int_mode="round",
                  keep_history=True, device=None, batch_cls=MPCBatch, rank=0, world=1, price_classes=None,
-                 n_classes=None, ev=None, **batch_kw):
+                 n_classes=None, ev=None, vehicles=False, day_offset=0, fleet_cls=EVFleet, **batch_kw):
         """price_classes ("type", or an int sequence [Nb] with `n_classes` = P; default None: one price for the
         community): the community's price classes (`resolve_price_classes`, `MPCBatch.set_price_classes`), shared by
         every episode and every sweep replica.  With P > 1 an action is a price per class: `step` takes [E][P] or
         [E][P][n], `sweep` [E][C][P] or [E][C][P][n] -- a 2-D `step` tensor and a 3-D `sweep` tensor then mean class
-        scalars, never price lists.  `n_classes`, `class_names` and `price_class_host` describe the map."""
+        scalars, never price lists.  `n_classes`, `class_names` and `price_class_host` describe the map.
+
+        vehicles=True: the homes' "ev" sections become an E-group fleet (`fleet_cls`, default `EVFleet`) stepped
+        after the homes at the same start indices and clocks, under the same price rows (a vehicle reads its owner
+        home's class's row); `day_offset`: the step of day of environment index 0.  Every sum then counts homes
+        plus vehicles; `ev_sums` ([E][3]) holds the vehicles' own rows of the last step, `ev_agg_hist` ([T][E][3],
+        with keep_history) their rows filed at each episode's own clock.  ValueError if no home has a vehicle.
+        `ev=` (a pre-built single fleet) is not taken: an E-group fleet with its own clocks is built here."""
         if ev is not None:
-            raise NotImplementedError("the vector environments do not take an EV fleet yet: the vehicles follow one "
-                                      "shared clock and price (DeviceAggregator(ev=...)), not per-episode ones")
+            raise NotImplementedError("the vector environments do not take a pre-built EV fleet: it follows one "
+                                      "shared clock and price (DeviceAggregator(ev=...)); vehicles=True builds the "
+                                      "episodes' own fleet from the homes' \"ev\" sections")
         if world > 1:
             raise ValueError("VectorAggregator runs on one rank: episodes are not sharded over ranks")
         E = int(episodes)
@@ -343,6 +372,28 @@ class VectorAggregator:
         self._hold = None
         self._gen = 0
         self.adopted = torch.zeros(E, dtype=torch.bool, device=dev)      # the episodes the last commit advanced
+        # the vehicles: fleet_cls is injectable for the same reason batch_cls is (tests/test_ev_vector_host.py)
+        self.fleet = self.ev_sums = self.ev_agg_hist = None
+        self.vehicle_max_rate = 0.0
+        self._sweep_fleets, self._held_fleets = {}, {}
+        if vehicles:
+            if not any(h.get("ev") is not None for h in homes):
+                raise ValueError("vehicles=True: no home of the community has an \"ev\" section")
+            self._fleet_args = (fleet_cls, dict(day_offset=int(day_offset), device=dev))
+            self.fleet = self._new_fleet(tou[:self.n_env], E)
+            self.ev_sums = self.fleet.sums
+            self.vehicle_max_rate = float(sum(float(h["ev"]["max_rate"]) for h in homes if h.get("ev") is not None))
+            if keep_history:
+                self.ev_agg_hist = torch.zeros((T, E, 3), dtype=torch.float64, device=dev)
+
+    def _new_fleet(self, tou, groups):
+        """A fleet of `groups` groups of the community's vehicles over `tou` (environment index 0 first), with the
+        owners' price classes."""
+        cls, kw = self._fleet_args
+        f = cls(self.homes, tou, start_index=0, groups=groups, **kw)
+        if self.n_classes > 1:
+            f.set_price_classes([int(self.price_class_host[i]) for i in f.owners], self.n_classes)
+        return f
 
     # ------------------------------------------------------------------ masks and keys
     def _mask(self, mask):
@@ -391,6 +442,11 @@ class VectorAggregator:
         self._set_keys(None if mask is None else m, seeds, start_indices)
         hm = self._homes_mask(m)
         b = self.batch
+        if self.fleet is not None:
+            self.fleet.reset_groups(m.contiguous())
+            if self.ev_agg_hist is not None:
+                self.ev_agg_hist.copy_(torch.where(m[None, :, None], torch.zeros((), dtype=torch.float64,
+                                                                                 device=self.device), self.ev_agg_hist))
         nan = torch.full((), float("nan"), dtype=torch.float64, device=self.device)
         self.clocks = torch.where(m, torch.zeros_like(self.clocks), self.clocks)
         self.parked = self.parked & ~m
@@ -460,15 +516,31 @@ class VectorAggregator:
             # fresh history row)
             self._row.fill_(float("nan"))
         b.step_episodes(self.seeds, self.starts, eff, noise=noise, hist=self._row)
+        if self.fleet is not None:           # after the homes, on the same stream, with the same keys and rows
+            self.fleet.set_reward_price(P.contiguous())
+            self.fleet.step_episodes(self.starts, eff)
         self._keep = eff
         return on
+
+    def _sums(self, on=None, idx=None):
+        """The live state's sums [E][3]: the homes', plus the vehicles' where there is a fleet (whose own rows are
+        then filed for the episodes `on` at the rows `idx`)."""
+        agg = self.batch.aggregate_groups()
+        if self.fleet is None:
+            return agg
+        agg = self.fleet.aggregate_onto(agg)
+        if self.ev_agg_hist is not None and on is not None:
+            a = self.ev_agg_hist
+            ai = idx.view(1, self.E, 1).expand(1, self.E, 3)
+            a.scatter_(0, ai, torch.where(on.view(1, self.E, 1), self.fleet.sums.view(1, self.E, 3), a.gather(0, ai)))
+        return agg
 
     def _file(self, on):
         """After a step of the episodes `on` (solved, or adopted): their sums, the step's rows filed at each
         episode's own clock, the clocks advanced.  -> [E][3]"""
         b = self.batch
-        agg = b.aggregate_groups()
         idx = self.clocks.clamp(0, self.num_timesteps - 1).to(torch.int64)
+        agg = self._sums(on, idx)
         if self.hist is not None:
             self._scatter(self.hist, self._row, idx, on)
         self._scatter(self.status_hist, b.status, idx, on)
@@ -494,6 +566,8 @@ class VectorAggregator:
             if self.n_classes > 1:
                 rb.set_price_classes(self.price_class_host, self.n_classes)       # the same map
             self._sweep_batches[C] = rb
+            if self.fleet is not None:       # the replica fleet: the live one's environment, C * E groups
+                self._sweep_fleets[C] = self._new_fleet(self.fleet.tou, C * self.E)
         for k in ("oat", "ghi", "tou", "start_index"):           # the live batch's environment (the same tensors)
             if hasattr(self.batch, k):
                 setattr(rb, k, getattr(self.batch, k))
@@ -548,11 +622,19 @@ class VectorAggregator:
             rb.hist_row.fill_(float("nan"))
         keys = (self.seeds.repeat(C), self.starts.repeat(C), eff.repeat(C))
         rb.step_episodes(*keys, hist=rb.hist_row if hold and self._row is not None else None)
+        rf = self._sweep_fleets.get(C)
+        if rf is not None:                   # the replica fleet: the same rows, copies and tiled keys
+            rf.set_reward_price(Pc.view(C * self.E, nc, -1) if nc > 1 else Pc.view(C * self.E, -1))
+            rf.replicate_from(self.fleet)
+            rf.step_episodes(keys[1], keys[2])
         if K > 1:
             return self._roll(rb, C, K, Pc, on, eff, keys, hold)
-        sums = rb.aggregate_groups().view(C, self.E, 3)
+        sums = rb.aggregate_groups()
+        if rf is not None:
+            sums = rf.aggregate_onto(sums)
+        sums = sums.view(C, self.E, 3)
         if hold:
-            self._hold = {"C": C, "P": Pc, "gen": self._gen, "on": on, "src": rb, "keys": keys}
+            self._hold = {"C": C, "P": Pc, "gen": self._gen, "on": on, "src": rb, "keys": keys, "fleet": rf}
         return sums.permute(1, 0, 2).contiguous()
 
     def _roll(self, rb, C, K, Pc, on, eff, keys, hold):
@@ -564,20 +646,31 @@ class VectorAggregator:
         if buf is None:
             buf = self._path_sums[(C, K)] = torch.zeros((K, C * E, 3), dtype=torch.float64, device=self.device)
         rb.aggregate_groups(out=buf[0])
+        rf = fsrc = self._sweep_fleets.get(C)
+        if rf is not None:
+            rf.aggregate_onto(buf[0])
         src = rb
         if hold:
             src = self._held.get(C)
             if src is None:
                 src = self._held[C] = HeldReplicas(rb)
             src.fill(rb)
+            if rf is not None:
+                fsrc = self._held_fleets.get(C)
+                if fsrc is None:
+                    fsrc = self._held_fleets[C] = HeldFleet(rf)
+                fsrc.fill(rf)
         idle = torch.full_like(eff, -1)
         for j in range(1, K):
-            clk = torch.where((eff >= 0) & (eff + j < T), eff + j, idle)
-            rb.step_episodes(keys[0], keys[1], clk.repeat(C))
+            clk = torch.where((eff >= 0) & (eff + j < T), eff + j, idle).repeat(C)
+            rb.step_episodes(keys[0], keys[1], clk)
             rb.aggregate_groups(out=buf[j])
+            if rf is not None:
+                rf.step_episodes(keys[1], clk)
+                rf.aggregate_onto(buf[j])
         self.sweep_steps = torch.where(eff >= 0, (T - eff).clamp(max=K), torch.zeros_like(eff))
         if hold:
-            self._hold = {"C": C, "P": Pc, "gen": self._gen, "on": on, "src": src, "keys": keys}
+            self._hold = {"C": C, "P": Pc, "gen": self._gen, "on": on, "src": src, "keys": keys, "fleet": fsrc}
         out = buf.view(K, C, E, 3).permute(2, 1, 0, 3).contiguous()
         self._paths = (out, buf)
         return out
@@ -669,6 +762,9 @@ class VectorAggregator:
         if self._row is not None:
             self._row.fill_(float("nan"))
         b.adopt_from(rb, ch, hist=self._row)
+        if self.fleet is not None:
+            self.fleet.set_reward_price(rows.contiguous())
+            self.fleet.adopt_from(h["fleet"], ch)
         self.adopted = on
         return on
 
@@ -684,7 +780,7 @@ class VectorAggregator:
         its own: the kernel reads it in every block and writes the clocks)."""
         if ran is None:
             ran = torch.where(on, self.clocks, torch.full_like(self.clocks, -1))
-        agg = self.batch.aggregate_groups()
+        agg = self._sums(on, ran.clamp(0, self.num_timesteps - 1).to(torch.int64))
         self.batch.env_file(st, ran, agg, hist=self._row)
         return agg
 
@@ -718,6 +814,11 @@ class VectorAggregator:
         self._set_keys(None if mask is None else m, host.get("seeds"), host.get("start_indices"))
         self.parked = self.parked & ~m
         self.batch.env_reset(st, m.contiguous())
+        if self.fleet is not None:
+            self.fleet.reset_groups(m.contiguous())
+            if self.ev_agg_hist is not None:
+                self.ev_agg_hist.copy_(torch.where(m[None, :, None], torch.zeros((), dtype=torch.float64,
+                                                                                 device=self.device), self.ev_agg_hist))
 
     # ------------------------------------------------------------------ plan observations
     def plan(self, keys, rows=(), out=None, classes=False):

@@ -632,7 +632,8 @@ int dragg_mpc_season_noise(const dragg_mpc_dims* dims, uint64_t seed, int32_t ho
    no iteration.  One wave per vehicle.  Nothing here reads or writes a home's arrays, and no home entry reads
    these.  M = n_vehicles vehicles; with dims.n_groups = G > 1 they are G consecutive replicas of M / G base
    vehicles (M % G == 0), vehicle r in group r / (M / G).  dims.n_homes is only checked (the usual dims check),
-   never read: a fleet passes its own M there.  Episode clocks and price classes do not reach the vehicles. */
+   never read: a fleet passes its own M there.  Episode clocks and price classes reach the vehicles through
+   dragg_mpc_ev_step_episodes (below); the three entries before it know one clock and one price row per group. */
 enum dragg_ev_param {           /* rows of dragg_mpc_ev.params [DRAGG_NEVP][M] */
     DRAGG_EVP_CAP = 0,          /* ev.capacity (kWh)                              */
     DRAGG_EVP_EMIN,             /* ev.capacity_lower * capacity                   */
@@ -716,6 +717,45 @@ int dragg_mpc_ev_step(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob,
    around the group, so a group's sums are those of a fleet of its vehicles alone, bit for bit.  No contraction,
    no atomics.  M == 0: zeros. */
 int dragg_mpc_ev_aggregate(const dragg_mpc_dims* dims, const dragg_mpc_ev* ev, double* out, void* stream);
+
+/* A step of a grouped fleet whose groups are episodes: dragg_mpc_ev_step's kernel behind
+   another prologue.  G = max(dims.n_groups, 1), Mb = M / G; vehicle r is base vehicle v = r % Mb of group g = r / Mb.
+     clock       t_g = ep.timestep ? ep.timestep[g] : timestep.  t_g < 0: the group is idle -- its waves leave
+                 before any write, no byte of its columns of vals, fc, status or obj changes.
+     start index s_g = ep.start_index ? ep.start_index[g] : problem.start_index.  A group whose window leaves the
+                 environment lists (s_g < 0 or s_g + t_g + H >= n_env) is idle too: dragg_mpc_step_episodes' rule,
+                 so an episode's homes and vehicles idle together.
+     day clock   ev.day_offset stays the step of day of environment index problem.start_index: stage k of group g
+                 lies at step of day (day_offset + (s_g - problem.start_index) + t_g + k) mod 24 dt, the
+                 non-negative remainder.
+     E_0         params EINIT where t_g == 0, else the vehicle's vals row DRAGG_EVK_E (per group).
+     price row   classes NULL or n_classes == 1: row g of reward_price [G][n_rp].  P classes: reward_price is
+                 [G][P][n_rp] and the vehicle reads row g P + clamp(price_class[v], 0, P - 1); price_class is [Mb]
+                 by BASE VEHICLE (its owner home's class).
+   ep.seed is not read: a vehicle draws no noise.  With every member of ep NULL and no classes the outputs are
+   dragg_mpc_ev_step's, bit for bit.  DRAGG_E_ARG: ep NULL, M % G != 0, n_classes outside 1 .. DRAGG_CLASS_MAX, a
+   NULL price_class with P > 1, and wherever dragg_mpc_ev_step returns it (its window check of the shared start
+   index and timestep applies where the member array that replaces them is NULL).  M == 0: a no-op. */
+int dragg_mpc_ev_step_episodes(const dragg_mpc_dims* dims, const dragg_mpc_problem* prob,
+                               const dragg_mpc_episodes* ep, const dragg_mpc_classes* classes,
+                               const dragg_mpc_ev* ev, int32_t timestep, void* stream);
+
+/* out[g][j] = base[g][j] + s[g][j], s exactly dragg_mpc_ev_aggregate's row of group g (the same summation order)
+   followed by one plain fp64 add, no contraction: homes-only sums plus the fleet's.  out may be base.  ev_out
+   (nullable, [G][3]) receives s.  M == 0: out = base, ev_out zeros. */
+int dragg_mpc_ev_aggregate_onto(const dragg_mpc_dims* dims, const dragg_mpc_ev* ev, const double* base, double* out,
+                                double* ev_out, void* stream);
+
+/* dragg_mpc_adopt for a fleet: the source fleet holds `copies` copies of the destination's E groups, copy-major;
+   group e takes from group choice[e] * E + e its Mb columns of vals, its vehicles' fc blocks, status and obj, bit
+   for bit.  A choice outside [0, copies) leaves every byte of group e untouched.  dst_dims: the destination
+   fleet's (n_homes = its M).  DRAGG_E_ARG: a NULL or misaligned array. */
+int dragg_mpc_ev_adopt(const dragg_mpc_dims* dst_dims, int32_t copies, const int32_t* choice,
+                       const dragg_mpc_ev* src_ev, const dragg_mpc_ev* dst_ev, void* stream);
+
+/* The masked groups (mask [G] bytes, nonzero: reset) start over: their columns of vals, their fc blocks and obj
+   become NaN (0x7ff8000000000000), their status 0; every other group keeps every byte. */
+int dragg_mpc_ev_reset(const dragg_mpc_dims* dims, const dragg_mpc_ev* ev, const uint8_t* mask, void* stream);
 
 #ifdef __cplusplus
 }
