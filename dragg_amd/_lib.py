@@ -401,6 +401,48 @@ def device_f64(x, device):
     return x.detach().to(device=device, dtype=torch.float64)
 
 
+def price_rows(rp, G, P, H, device, what="a batch"):
+    """A reward price for G groups of P price classes at horizon H -> (the rows flat, as a contiguous float64
+    tensor on `device`, and n, the entries per row).  P > 1: [G][P][n], [G][P] (class scalars; a 2-D tensor of
+    that shape always means this), or one [P] / [P][n] for every group.  Else G > 1: [G][n], or one list for every
+    group.  Else one list.  Host values, or a tensor: a contiguous float64 tensor already on `device` comes back
+    as it is (no copy).  ValueError for another shape, or for n != 1 and n < H."""
+    rp = device_f64(rp if hasattr(rp, "shape") else list(rp), device)
+    G = max(G, 1)
+    if P > 1:
+        shape = list(rp.shape)
+        if shape == [G, P]:
+            rp = rp.reshape(G, P, 1)
+        elif shape == [P] or (len(shape) == 2 and shape[0] == P):
+            rp = rp.reshape(1, P, -1).expand(G, P, -1)
+        if rp.dim() != 3 or list(rp.shape[:2]) != [G, P] or rp.shape[2] < 1:
+            raise ValueError(f"{what} of {G} groups and {P} price classes takes reward prices [{G}][{P}], "
+                             f"[{G}][{P}][n], [{P}] or [{P}][n], not {shape}")
+    elif G > 1:
+        if rp.dim() < 2:
+            rp = rp.reshape(1, -1).expand(G, -1)
+        if rp.dim() != 2 or rp.shape[0] != G:
+            raise ValueError(f"{what} of {G} groups takes reward prices [{G}][n] or [n], not {list(rp.shape)}")
+    n = rp.numel() // (G * P)
+    if n != 1 and n < H:
+        # np.array(rp[:H]) + tou[:H] raises in the reference (mpc_calc.py:353)
+        raise ValueError(f"operands could not be broadcast together: reward_price has {n} entries, horizon is {H}")
+    return rp.reshape(-1).contiguous(), n
+
+
+def device_arg(x, name, device, dtype, shape=None, numel=None):
+    """`x` if it is what a launch reads where it lies: a contiguous tensor on `device` of `dtype` (or of one of a
+    tuple of dtypes), of `shape` or of `numel` entries where given.  ValueError otherwise."""
+    import torch
+    dtypes = dtype if type(dtype) is tuple else (dtype,)
+    if not torch.is_tensor(x) or x.dtype not in dtypes or (shape is not None and x.shape != shape) \
+            or (numel is not None and x.numel() != numel) or x.device != device or not x.is_contiguous():
+        size = list(shape) if shape is not None else (f"of {numel} entries" if numel is not None else "")
+        raise ValueError(f"{name} must be a contiguous device tensor {size} of {dtypes[0]}, not "
+                         f"{getattr(x, 'dtype', type(x))} {list(getattr(x, 'shape', []))}")
+    return x
+
+
 def episode_mask(mask, E):
     """None (every episode), a bool sequence / array / tensor [E], or episode indices -> bool [E]: a bool
     tensor as it is (wherever it lives: no host round trip), anything else as a numpy array."""

@@ -15,6 +15,10 @@ home on the host.  Here the community's state never leaves the GPU:
 Homes are sharded by stride (rank r solves global homes r, r + world, r + 2 world, ...: every
 shard carries the community's type mix); the season-noise stream is keyed by the GLOBAL home
 index, so results do not depend on the shard layout.
+
+The batch and, with `ev=`, the fleet are held as one unit (`members.Members`): the reward price, snapshots, the
+fleet's part of a checkpoint and a sweep's replicas go through it.  The step itself, its history rows and the lag
+mode's bookkeeping address the batch and the fleet apart, in a fixed order of launches.
 """
 import os
 import zlib
@@ -23,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .members import FLEET_ARRAYS, Held, Members
 from .mpc import MPCBatch
 
 
@@ -34,17 +39,8 @@ def shard_index(n, rank, world):
     return np.arange(rank, n, world)
 
 
-class HeldStep:
-    """A sweep's first step, cloned out of its replica batch before the replicas move on: the arrays
-    `MPCBatch.adopt_from` reads."""
-
-    def __init__(self, rb, row):
-        self.N, self.H, self.groups, self.hist_row = rb.N, rb.H, getattr(rb, "groups", 1), row
-        # (fc is a view of fc_store where a batch has one: MPCBatch)
-        for k in ("vals", "fc_store", "status", "iters", "obj", "relax_obj", "int_path"):
-            v = getattr(rb, k, None)
-            setattr(self, k, v.clone() if v is not None else None)
-        self.fc = self.fc_store.permute(1, 2, 0) if self.fc_store is not None else rb.fc.clone()
+# a checkpoint's keys of the fleet's state arrays (members.FLEET_ARRAYS, in that order)
+EV_STATE_KEYS = ("ev_vals", "ev_fc", "ev_status", "ev_obj")
 
 
 class DeviceAggregator:
@@ -63,12 +59,10 @@ class DeviceAggregator:
         self.device = dev
         # batch_cls is injectable only so the multi-rank glue can be exercised with gloo on
         # CPU (tests/test_distributed.py); the solver itself is MPCBatch (HIP, no fallback).
-        self._batch_cls = batch_cls
         self._batch_kw = dict(int_mode=int_mode, seed=seed, home_offset=rank, home_stride=world, max_iter=max_iter,
                               check_every=check_every, device=dev, template_home=homes[0] if homes else None,
                               **({"exact": True} if exact else {}))
         self.batch = batch_cls(self.homes, oat, ghi, tou, start_index, reward_price, **self._batch_kw)
-        self._sweep_batches = {}     # G -> the G-replica batch of sweep()
         self.sweep_counts = None
         # a held sweep (sweep(hold=True)): its first step's replicas, kept for commit(); `_gen` counts the
         # moves of the live state (a step, a restore, a loaded checkpoint, a commit), which void a hold
@@ -108,6 +102,8 @@ class DeviceAggregator:
         # history; its three sums of step t are added to agg_hist[t] exactly once, on top of the homes-only row,
         # before any all-reduce
         self.ev = ev
+        # the homes and the fleet as one unit (members.py): the price, snapshots and sweeps go through it
+        self.members = Members(self.batch, ev, homes=self.homes, batch_args=(batch_cls, self._batch_kw))
         self._ev_pending = []        # steps whose agg_hist row still lacks the fleet's row (lag mode)
         if ev is not None:
             from . import _lib as _L
@@ -131,6 +127,9 @@ class DeviceAggregator:
             self._flag_stream = torch.cuda.Stream(device=dev) if pin else None
             self._flag_src = [torch.cuda.Event() if pin else None for _ in range(K)]
             self.lag_from = None             # the first step run in lag mode
+
+    # G -> the G-replica batch of sweep() (a view of the unit's replicas: drop one there)
+    _sweep_batches = property(lambda self: {k: r.batch for k, r in self.members.replicas.items()})
 
     FLAG_LAG = 2                 # adaptive start: steps the host may run ahead of the last flag it reads
 
@@ -293,26 +292,18 @@ class DeviceAggregator:
         t = L.device_f64(rp, self.device).reshape(-1).contiguous()
         if self.world > 1:
             torch.distributed.broadcast(t, src=src, group=self.group)
-        self.batch.set_reward_price(t)
-        if self.ev is not None:
-            self.ev.set_reward_price(t)
+        self.members.set_reward_price(t)
         return t
 
     def snapshot(self):
         self.drain()
-        if self.ev is not None:
-            return self.timestep, self.batch.vals.clone(), self.batch.fc.clone(), self.ev.snapshot()
-        return self.timestep, self.batch.vals.clone(), self.batch.fc.clone()
+        return (self.timestep,) + self.members.snapshot()
 
     def restore(self, snap):
         self.drain()
-        t, vals, fc = snap[:3]
         self._gen += 1
-        self.timestep = t
-        self.batch.vals.copy_(vals)
-        self.batch.fc.copy_(fc)
-        if self.ev is not None:
-            self.ev.restore(snap[3])
+        self.timestep = snap[0]
+        self.members.restore(snap[1:])
 
     def forecast(self, steps, noise_fn=None):
         """Solve every home `steps` timesteps ahead under the current reward price without
@@ -340,19 +331,6 @@ class DeviceAggregator:
     # include/dragg_mi355x.h) holds G replicas of this shard's homes, replica g solved under prices[g]
     # with the base homes' season noise.  The live state is fanned out to the replicas by one kernel
     # and never written: no snapshot, no restore.
-    def _sweep_batch(self, G):
-        rb = self._sweep_batches.get(G)
-        if rb is None:
-            rb = self._batch_cls(self.homes, None, None, None, 0, (0.0,), groups=G, **self._batch_kw)
-            self._sweep_batches[G] = rb
-        # the live batch's environment, as it is now (the same device tensors)
-        for k in ("oat", "ghi", "tou", "start_index"):
-            if hasattr(self.batch, k):
-                setattr(rb, k, getattr(self.batch, k))
-        if hasattr(self.batch, "dims"):
-            rb.dims.n_env = self.batch.dims.n_env
-        return rb
-
     def sweep(self, prices, steps, noise_fn=None, src=0, hold=False):
         """The community's response to each of G candidate reward-price lists (`prices` [G][n], n == 1
         or n >= H) over `steps` timesteps ahead, nothing committed: a device tensor [G][steps][agg_load,
@@ -382,9 +360,10 @@ class DeviceAggregator:
         if self.world > 1:
             torch.distributed.broadcast(P, src=src, group=self.group)
         G, steps = int(P.shape[0]), int(steps)
-        rb = self._sweep_batch(G)
-        rb.set_reward_price(P)
-        rb.replicate_from(self.batch)
+        r = self.members.replica(G)
+        r.set_reward_price(P)
+        r.replicate_from(self.members)
+        rb = r.batch
         out = torch.zeros((G, steps, 3), dtype=torch.float64, device=self.device)
         counts = torch.zeros((3, G), dtype=torch.int64, device=self.device)
         row = None
@@ -398,8 +377,8 @@ class DeviceAggregator:
             if hasattr(rb, "int_path"):
                 counts += L.path_counts(rb.int_path.view(G, -1), 1)
             if s == 0 and row is not None:
-                self._hold = {"t": self.timestep, "G": G, "P": P, "gen": self._gen,
-                              "src": rb if steps == 1 else HeldStep(rb, row)}
+                unit = r if steps == 1 else Held(r).fill(r, row)
+                self._hold = {"t": self.timestep, "G": G, "P": P, "gen": self._gen, "unit": unit, "src": unit.batch}
         if self.world > 1:
             torch.distributed.all_reduce(out, group=self.group)
             torch.distributed.all_reduce(counts, group=self.group)
@@ -438,7 +417,7 @@ class DeviceAggregator:
         ch = self._choices.get(G)
         if ch is None:
             ch = self._choices[G] = torch.arange(G, dtype=torch.int32, device=self.device)
-        self.batch.adopt_from(h["src"], ch[int(g):int(g) + 1], hist=self.hist[t] if self.hist is not None else None)
+        self.members.adopt_from(h["unit"], ch[int(g):int(g) + 1], hist=self.hist[t] if self.hist is not None else None)
         self.status_hist[t].copy_(self.batch.status, non_blocking=True)
         if hasattr(self.batch, "int_path"):
             self.path_hist[t].copy_(self.batch.int_path, non_blocking=True)
@@ -478,7 +457,7 @@ class DeviceAggregator:
         """The planned curves of the held sweep's G replicas -> (curve [G][nk][H], count, stats [G][nr][4]):
         candidate g's open-loop response over the whole horizon, where `sweep` returns its first-step sums.
         The held step is the sweep's first (with steps == 1 the replica batch itself, with more the arrays
-        cloned after it: `HeldStep`), so replica g's rows are those `plan()` gives after `commit(g)`, bit for
+        copied after it: `members.Held`), so replica g's rows are those `plan()` gives after `commit(g)`, bit for
         bit.  All-reduced over the ranks as `plan`.  ValueError where `holds()` is false."""
         if not self.holds():
             raise ValueError("sweep_plan: no sweep of the live state is held (sweep(..., hold=True) first)")
@@ -502,10 +481,9 @@ class DeviceAggregator:
                  "deferred": torch.as_tensor(self._deferred, dtype=torch.long),
                  "hist": self.hist[:t].cpu() if self.hist is not None else None}
         if self.ev is not None:
-            state.update({"ev_m": int(self.ev.M), "ev_vals": self.ev.vals.cpu(), "ev_fc": self.ev.fc_store.cpu(),
-                          "ev_status": self.ev.status.cpu(), "ev_obj": self.ev.obj.cpu(),
-                          "ev_hist": self.ev_hist[:t].cpu(), "ev_status_hist": self.ev_status_hist[:t].cpu(),
-                          "ev_agg_hist": self.ev_agg_hist[:t].cpu()})
+            state.update({key: getattr(self.ev, k).cpu() for key, k in zip(EV_STATE_KEYS, FLEET_ARRAYS)})
+            state.update({"ev_m": int(self.ev.M), "ev_hist": self.ev_hist[:t].cpu(),
+                          "ev_status_hist": self.ev_status_hist[:t].cpu(), "ev_agg_hist": self.ev_agg_hist[:t].cpu()})
         tmp = path + ".tmp"
         torch.save(state, tmp)
         os.replace(tmp, path)                 # a crash mid-write leaves the previous checkpoint
@@ -541,7 +519,7 @@ class DeviceAggregator:
         if self.hist is not None and st["hist"] is not None:
             self.hist[:t].copy_(st["hist"])
         if self.ev is not None:
-            self.ev.restore((st["ev_vals"], st["ev_fc"], st["ev_status"], st["ev_obj"]))
+            self.ev.restore([st[key] for key in EV_STATE_KEYS])
             self.ev_hist[:t].copy_(st["ev_hist"])
             self.ev_status_hist[:t].copy_(st["ev_status_hist"])
             self.ev_agg_hist[:t].copy_(st["ev_agg_hist"])

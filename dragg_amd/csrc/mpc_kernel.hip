@@ -5334,12 +5334,10 @@ __global__ __launch_bounds__(REP_NT) void env_file_kernel(EnvArgs a) {
     }
 }
 
-// reset: group g's part of every row takes the segment's `fill` (4-byte units: the int32 stores, filled with
-// its low half, 0).  A mask byte of 0 is idle.
-__global__ __launch_bounds__(REP_NT) void env_reset_kernel(EnvArgs a) {
-    const int g = (int)blockIdx.y;
-    if (!__builtin_amdgcn_readfirstlane((int)a.mask[g])) return;
-    seg_walk(a.segs, [&](const Seg& s, long long r, long long i, auto unit) {
+// group g's part of every row of every segment takes the segment's `fill` (4-byte units: the int32 stores, filled
+// with its low half, 0)
+DEV void seg_fill_group(const Segs& segs, int g) {
+    seg_walk(segs, [&](const Seg& s, long long r, long long i, auto unit) {
         using T = decltype(unit);
         T v;
         if constexpr (sizeof(T) == 16) {
@@ -5350,6 +5348,13 @@ __global__ __launch_bounds__(REP_NT) void env_reset_kernel(EnvArgs a) {
         }
         *seg_at<T>(s.dst, r * s.dst_stride + g * s.group_bytes, i) = v;
     });
+}
+
+// reset: the fill above for every masked group.  A mask byte of 0 is idle.
+__global__ __launch_bounds__(REP_NT) void env_reset_kernel(EnvArgs a) {
+    const int g = (int)blockIdx.y;
+    if (!__builtin_amdgcn_readfirstlane((int)a.mask[g])) return;
+    seg_fill_group(a.segs, g);
     if (blockIdx.x == 0 && threadIdx.x == 0) env_setpoint(a, g, 0, a.start_load, a.start_load, 0.0, true);
 }
 
@@ -5361,17 +5366,7 @@ struct EvResetArgs {
 __global__ __launch_bounds__(REP_NT) void ev_reset_kernel(EvResetArgs a) {
     const int g = (int)blockIdx.y;
     if (!__builtin_amdgcn_readfirstlane((int)a.mask[g])) return;
-    seg_walk(a.segs, [&](const Seg& s, long long r, long long i, auto unit) {
-        using T = decltype(unit);
-        T v;
-        if constexpr (sizeof(T) == 16) {
-            const unsigned lo = (unsigned)s.fill, hi = (unsigned)(s.fill >> 32);
-            v = uint4{lo, hi, lo, hi};
-        } else {
-            v = (T)s.fill;
-        }
-        *seg_at<T>(s.dst, r * s.dst_stride + g * s.group_bytes, i) = v;
-    });
+    seg_fill_group(a.segs, g);
 }
 
 // dragg_mpc_select_paths: the choice over K-step rollouts.  Block e (one wave) owns episode e, a lane one of its
@@ -6691,7 +6686,44 @@ int dragg_mpc_ev_lds_bytes(const dragg_mpc_dims* dims) {
     return ev_block_lds(dims->horizon) > (size_t)LDS_DYN_MAX ? DRAGG_E_HORIZON : (int)ev_block_lds(dims->horizon);
 }
 
-static bool ev_state_ok(const dragg_mpc_ev* ev) { return ev->params && ev->vals && ev->fc && ev->status && ev->obj; }
+// A fleet's four state arrays in the mover's order: where the pointer lies in dragg_mpc_ev, the array's bytes per
+// vehicle and row (times H where `per_stage`), its rows, its element bytes and the bits a reset fills it with
+struct EvArray {
+    size_t member;
+    long long col;
+    bool per_stage;
+    int rows;
+    long long elem;
+    unsigned long long fill;
+};
+constexpr unsigned long long NAN_BITS = 0x7FF8000000000000ull;      // (as dragg_mpc_env_reset's)
+static const EvArray EV_STATE[] = {{offsetof(dragg_mpc_ev, fc), DRAGG_NEVK * 8, true, 1, 8, NAN_BITS},
+                                   {offsetof(dragg_mpc_ev, vals), 8, false, DRAGG_NEVV, 8, NAN_BITS},
+                                   {offsetof(dragg_mpc_ev, obj), 8, false, 1, 8, NAN_BITS},
+                                   {offsetof(dragg_mpc_ev, status), 4, false, 1, 4, 0}};
+static void* ev_array(const dragg_mpc_ev* ev, const EvArray& x) {
+    return *reinterpret_cast<void* const*>(reinterpret_cast<const char*>(ev) + x.member);
+}
+
+static bool ev_arrays_ok(const dragg_mpc_ev* ev) {
+    for (const EvArray& x : EV_STATE)
+        if (!ev_array(ev, x)) return false;
+    return true;
+}
+
+static bool ev_state_ok(const dragg_mpc_ev* ev) { return ev->params && ev_arrays_ok(ev); }
+
+// the fleet's arrays as mover segments over groups of Mb vehicles: src (Ms vehicles; null: a fill) -> dst (Md)
+static bool ev_state_segs(Segs& segs, const dragg_mpc_ev* src, const dragg_mpc_ev* dst, long long Ms, long long Md,
+                          long long Mb, int H) {
+    bool ok = true;
+    for (const EvArray& x : EV_STATE) {
+        const long long col = x.per_stage ? x.col * H : x.col;
+        ok = seg_add(segs, src ? ev_array(src, x) : nullptr, ev_array(dst, x), Ms * col, Md * col, Mb * col, x.rows,
+                     x.elem, src ? 0 : x.fill) && ok;
+    }
+    return ok;
+}
 
 int dragg_mpc_ev_solve_explicit(const dragg_mpc_dims* dims, const dragg_mpc_ev* ev, const dragg_mpc_ev_explicit* in,
                                 void* stream) {
@@ -6789,22 +6821,12 @@ int dragg_mpc_ev_adopt(const dragg_mpc_dims* dst_dims, int32_t copies, const int
     if (dst_dims->n_groups < 0 || E > 65535 || Md % E != 0 || (long long)src_ev->n_vehicles != copies * Md)
         return DRAGG_E_ARG;
     if (Md == 0) return DRAGG_OK;
-    if (!src_ev->vals || !src_ev->fc || !src_ev->status || !src_ev->obj || !dst_ev->vals || !dst_ev->fc ||
-        !dst_ev->status || !dst_ev->obj)
-        return DRAGG_E_ARG;
-    const long long Mb = Md / E;
+    if (!ev_arrays_ok(src_ev) || !ev_arrays_ok(dst_ev)) return DRAGG_E_ARG;
     AdoptArgs a{};
     a.copies = copies;
     a.E = E;
     a.choice = choice;
-    bool ok = true;
-    auto seg = [&](const void* s, void* d, long long col, int rows, long long elem) {
-        ok = seg_add(a.segs, s, d, copies * Md * col, Md * col, Mb * col, rows, elem) && ok;
-    };
-    seg(src_ev->fc, dst_ev->fc, (long long)DRAGG_NEVK * dst_dims->horizon * 8, 1, 8);
-    seg(src_ev->vals, dst_ev->vals, 8, DRAGG_NEVV, 8);
-    seg(src_ev->obj, dst_ev->obj, 8, 1, 8);
-    seg(src_ev->status, dst_ev->status, 4, 1, 4);
+    const bool ok = ev_state_segs(a.segs, src_ev, dst_ev, copies * Md, Md, Md / E, dst_dims->horizon);
     return ok ? seg_launch(adopt_kernel, a, E, stream) : DRAGG_E_ARG;
 }
 
@@ -6814,20 +6836,11 @@ int dragg_mpc_ev_reset(const dragg_mpc_dims* dims, const dragg_mpc_ev* ev, const
     const long long M = ev->n_vehicles;
     if (dims->n_groups < 0 || G > 65535 || M % G != 0) return DRAGG_E_ARG;
     if (M == 0) return DRAGG_OK;
-    if (!ev->vals || !ev->fc || !ev->status || !ev->obj) return DRAGG_E_ARG;
-    const long long Mb = M / G;
-    const unsigned long long nan = 0x7FF8000000000000ull;
+    if (!ev_arrays_ok(ev)) return DRAGG_E_ARG;
     EvResetArgs a{};
     a.mask = mask;
-    bool ok = true;
-    auto seg = [&](void* d, long long col, int rows, long long elem, unsigned long long fill) {
-        ok = seg_add(a.segs, nullptr, d, M * col, M * col, Mb * col, rows, elem, fill) && ok;
-    };
-    seg(ev->fc, (long long)DRAGG_NEVK * dims->horizon * 8, 1, 8, nan);
-    seg(ev->vals, 8, DRAGG_NEVV, 8, nan);
-    seg(ev->obj, 8, 1, 8, nan);
-    seg(ev->status, 4, 1, 4, 0);
-    return ok ? seg_launch(ev_reset_kernel, a, G, stream) : DRAGG_E_ARG;
+    return ev_state_segs(a.segs, nullptr, ev, M, M, M / G, dims->horizon) ? seg_launch(ev_reset_kernel, a, G, stream)
+                                                                            : DRAGG_E_ARG;
 }
 
 }  // extern "C"

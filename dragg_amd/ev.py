@@ -10,13 +10,16 @@ The reference has no vehicle; the model is this project's (DESIGN.md section 3.1
 The vehicle is one more separable block of its home: the price is an input and nothing else couples it to the
 home's LP, so the fleet is a batch of its own (one wave per vehicle) whose three sums are added to the homes'.
 `pack_evs` and `ev_schedule` are plain numpy (the schedule arithmetic the kernel's prologue does); `EVFleet` holds
-the device state and has no CPU fallback.
+the device state and has no CPU fallback.  The aggregators move a fleet together with its homes' batch through
+`members.Members` (prices, episode steps, sums, replicas, adoption, reset); the arrays that make a fleet's state are
+named once, `members.FLEET_ARRAYS`.
 """
 import ctypes
 
 import numpy as np
 
 from . import _lib as L
+from .members import FLEET_ARRAYS
 from .mpc import hems_dims
 
 EV_FIELDS = ("capacity", "capacity_lower", "capacity_upper", "max_rate", "ch_eff", "disch_eff", "e_ev_init", "v2g",
@@ -195,31 +198,10 @@ class EVFleet:
         self.set_reward_price(torch.zeros((self.groups, P) if P > 1 else (self.groups, 1), dtype=torch.float64))
 
     def set_reward_price(self, rp):
-        """As MPCBatch.set_reward_price: one list, or [G][n] for a grouped fleet; with P price classes
-        (`set_price_classes`) [G][P][n], or [G][P] (class scalars)."""
-        rp = L.device_f64(rp if hasattr(rp, "shape") else [float(v) for v in rp], self.device)
-        G, P = self.groups, self.n_classes
-        if P > 1:
-            if tuple(rp.shape) == (G, P):
-                rp = rp.reshape(G, P, 1)
-            if rp.dim() != 3 or tuple(rp.shape[:2]) != (G, P) or rp.shape[2] < 1:
-                raise ValueError(f"a fleet of {G} groups and {P} price classes takes reward prices [{G}][{P}] or "
-                                 f"[{G}][{P}][n], not {list(rp.shape)}")
-            n = int(rp.shape[2])
-        elif G > 1:
-            if rp.dim() < 2:
-                rp = rp.reshape(1, -1).expand(G, -1)
-            if rp.dim() != 2 or rp.shape[0] != G:
-                raise ValueError(f"a fleet of {G} groups takes reward prices [{G}][n], not {list(rp.shape)}")
-            n = int(rp.shape[1])
-        else:
-            rp = rp.reshape(-1)
-            n = int(rp.numel())
-        if n != 1 and n < self.H:
-            raise ValueError(f"operands could not be broadcast together: reward_price has {n} entries, "
-                             f"horizon is {self.H}")
-        self.rp = rp.reshape(-1).contiguous().clone()
-        self.dims.n_rp = n
+        """As MPCBatch.set_reward_price (`_lib.price_rows`): one list, or [G][n] for a grouped fleet; with P price
+        classes (`set_price_classes`) [G][P][n], [G][P] (class scalars), or one [P] / [P][n] for every group."""
+        rp, self.dims.n_rp = L.price_rows(rp, self.groups, self.n_classes, self.H, self.device, "a fleet")
+        self.rp = rp.clone()                    # (a copy of its own: the caller's rows may be rewritten)
 
     # ------------------------------------------------------------------ structs and launches
     def _ev(self):
@@ -242,10 +224,8 @@ class EVFleet:
         every group.  The day clock follows the start index (`ev_episode_day_step`).  No synchronisation."""
         import torch
         for name, x in (("starts", starts), ("clocks", clocks)):
-            if x is not None and (not torch.is_tensor(x) or x.device != self.device or x.dtype != torch.int32
-                                  or tuple(x.shape) != (self.groups,) or not x.is_contiguous()):
-                raise ValueError(f"{name} must be a contiguous device tensor [{self.groups}] of {torch.int32}, not "
-                                 f"{getattr(x, 'dtype', type(x))} {list(getattr(x, 'shape', []))}")
+            if x is not None:
+                L.device_arg(x, name, self.device, torch.int32, (self.groups,))
         ep = L.Episodes(seed=None, start_index=L.ptr(starts), timestep=L.ptr(clocks))
         cls = L.Classes(n_classes=int(self.n_classes), price_class=L.ptr(self.price_class))
         L.check(self.lib.dragg_mpc_ev_step_episodes(self.dims, self._problem(), ep, cls, self._ev(), int(t),
@@ -284,9 +264,7 @@ class EVFleet:
         import torch
         out = base if out is None else out
         for name, x in (("base", base), ("out", out)):
-            if not torch.is_tensor(x) or x.device != self.device or x.dtype != torch.float64 \
-                    or x.numel() != self.groups * 3 or not x.is_contiguous():
-                raise ValueError(f"aggregate_onto: {name} must be a contiguous device float64 tensor [{self.groups}][3]")
+            L.device_arg(x, f"aggregate_onto: {name}", self.device, torch.float64, numel=self.groups * 3)
         L.check(self.lib.dragg_mpc_ev_aggregate_onto(self.dims, self._ev(), L.ptr(base), L.ptr(out), L.ptr(self.sums),
                                                      L.stream_ptr(stream, self.device)))
         return out
@@ -302,9 +280,7 @@ class EVFleet:
         if copies < 1 or src.M != copies * self.M or src.H != self.H:
             raise ValueError(f"adopt_from: a fleet of {self.M} vehicles (H = {self.H}) cannot adopt from {src.M} "
                              f"vehicles (H = {src.H}): the source holds whole copies of it")
-        if not torch.is_tensor(choice) or choice.device != self.device or choice.dtype != torch.int32 \
-                or tuple(choice.shape) != (self.groups,) or not choice.is_contiguous():
-            raise ValueError(f"choice must be a contiguous device tensor [{self.groups}] of {torch.int32}")
+        L.device_arg(choice, "choice", self.device, torch.int32, (self.groups,))
         s = L.Ev(params=None, vals=L.ptr(src.vals), fc=L.ptr(src.fc_store), status=L.ptr(src.status),
                  obj=L.ptr(src.obj), day_offset=self.day_offset, n_vehicles=src.M)
         L.check(self.lib.dragg_mpc_ev_adopt(self.dims, copies, L.ptr(choice), s, self._ev(),
@@ -315,18 +291,16 @@ class EVFleet:
         """Start the masked groups (`mask`: contiguous device bool [G]) over (dragg_mpc_ev_reset): their vals
         columns, fc blocks and obj NaN, their status 0 -- the state of a new fleet; the others keep every byte."""
         import torch
-        if not torch.is_tensor(mask) or mask.device != self.device or mask.dtype != torch.bool \
-                or tuple(mask.shape) != (self.groups,) or not mask.is_contiguous():
-            raise ValueError(f"mask must be a contiguous device bool tensor [{self.groups}]")
+        L.device_arg(mask, "mask", self.device, torch.bool, (self.groups,))
         L.check(self.lib.dragg_mpc_ev_reset(self.dims, self._ev(), L.ptr(mask), L.stream_ptr(stream, self.device)))
         self._keep = (mask,)
 
     def snapshot(self):
-        return self.vals.clone(), self.fc_store.clone(), self.status.clone(), self.obj.clone()
+        return tuple(getattr(self, k).clone() for k in FLEET_ARRAYS)
 
     def restore(self, snap):
-        for dst, src in zip((self.vals, self.fc_store, self.status, self.obj), snap):
-            dst.copy_(src)
+        for k, src in zip(FLEET_ARRAYS, snap):
+            getattr(self, k).copy_(src)
 
     def replicate_from(self, base):
         """A grouped fleet's state: every group a copy of `base`'s (a fleet of the same vehicles, one group).

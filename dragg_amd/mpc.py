@@ -15,6 +15,7 @@ import torch
 from . import _lib as L
 
 TAP_TEMP = 15.0  # mpc_calc.py:181
+SEED_DTYPES = (torch.int64, getattr(torch, "uint64", torch.int64))      # a seed's bits are the key, either way
 
 
 def _f(x):
@@ -186,46 +187,12 @@ class MPCBatch:
     def set_reward_price(self, rp):
         """The redis 'reward_price' list (mpc_calc.py:630-637): host values, or a device tensor
         (e.g. an RL action broadcast over RCCL), taken without a host round trip.  A grouped batch
-        takes [G][n], one list per group (every row n entries), or one list for every group."""
-        G = getattr(self, "groups", 1)
-        P = getattr(self, "n_classes", 1)
-        if P > 1:
-            # price classes: P rows per group, [G][P][n] on the device.  [G][P] (class scalars; a 2-D tensor of
-            # that shape always means this) or [G][P][n], or one [P] / [P][n] for every group
-            rp = L.device_f64(rp, self.device)
-            shape = tuple(rp.shape)
-            if shape == (G, P):
-                rp = rp.reshape(G, P, 1)
-            elif shape == (P,):
-                rp = rp.reshape(1, P, 1).expand(G, P, 1)
-            elif len(shape) == 2 and shape[0] == P:
-                rp = rp.reshape(1, P, -1).expand(G, P, -1)
-            if rp.dim() != 3 or tuple(rp.shape[:2]) != (G, P) or rp.shape[2] < 1:
-                raise ValueError(f"a batch of {G} groups and {P} price classes takes reward prices [{G}][{P}], "
-                                 f"[{G}][{P}][n], [{P}] or [{P}][n], not {list(shape)}")
-            n = rp.shape[2]
-            rp = rp.reshape(-1).contiguous()
-        elif G > 1:
-            rp = L.device_f64(rp, self.device)
-            if rp.dim() < 2:
-                rp = rp.reshape(1, -1).expand(G, -1)
-            if rp.dim() != 2 or rp.shape[0] != G:
-                raise ValueError(f"a batch of {G} groups takes reward prices [{G}][n], not {list(rp.shape)}")
-            n = rp.shape[1]
-            rp = rp.reshape(-1).contiguous()
-        elif torch.is_tensor(rp):
-            rp = rp.detach().to(device=self.device, dtype=torch.float64).reshape(-1).contiguous()
-            n = rp.numel()
-        else:
-            rp = np.asarray([float(v) for v in rp], dtype=float)
-            n = len(rp)
-        if n != 1 and n < self.H:
-            # np.array(rp[:H]) + tou[:H] raises in the reference (mpc_calc.py:353)
-            raise ValueError(f"operands could not be broadcast together: reward_price has {n} "
-                             f"entries, horizon is {self.H}")
+        takes [G][n], one list per group (every row n entries), or one list for every group; with price classes
+        [G][P], [G][P][n], or one [P] / [P][n] for every group (`_lib.price_rows`)."""
+        rp, n = L.price_rows(rp, getattr(self, "groups", 1), getattr(self, "n_classes", 1), self.H, self.device)
         if getattr(self, "lag", None) is not None:
             self.drain()                     # (as in set_environment: the side pass reads self.rp)
-        self.rp = rp if torch.is_tensor(rp) else torch.tensor(rp, dtype=torch.float64, device=self.device)
+        self.rp = rp
         self.dims.n_rp = n
         if self.workspace is not None or hasattr(self, "vals"):
             self._ensure_workspace()
@@ -488,10 +455,7 @@ class MPCBatch:
         if copies < 1 or src.N != copies * self.N or src.H != self.H:
             raise ValueError(f"adopt_from: a batch of {self.N} homes (H = {self.H}) cannot adopt from "
                              f"{src.N} homes (H = {src.H}): the source holds whole copies of it")
-        if not torch.is_tensor(choice) or choice.device != self.device or choice.dtype != torch.int32 \
-                or tuple(choice.shape) != (E,) or not choice.is_contiguous():
-            raise ValueError(f"choice must be a contiguous device tensor [{E}] of {torch.int32}, not "
-                             f"{getattr(choice, 'dtype', type(choice))} {list(getattr(choice, 'shape', []))}")
+        L.device_arg(choice, "choice", self.device, torch.int32, (E,))
         row = getattr(src, "hist_row", None)
         with torch.cuda.device(self.device):
             self.drain(stream)
@@ -542,8 +506,7 @@ class MPCBatch:
                             ("prices", prices, torch.float64), ("score", score, torch.float64)):
             if x is None and name == "score":
                 continue
-            if not torch.is_tensor(x) or x.device != dev or x.dtype != dt or not x.is_contiguous():
-                raise ValueError(f"select_paths: {name} must be a contiguous device tensor of {dt}")
+            L.device_arg(x, f"select_paths: {name}", dev, dt)
         if sums.dim() != 3 or sums.shape[2] != 3 or sums.shape[1] < E or sums.shape[1] % E or sums.shape[0] < 1:
             raise ValueError(f"select_paths takes sums [K][C * {E}][3], not {list(sums.shape)}")
         K, CE = int(sums.shape[0]), int(sums.shape[1])
@@ -571,9 +534,8 @@ class MPCBatch:
                 if getattr(self, "agg_groups", None) is None:
                     self.agg_groups = torch.zeros((self.groups, 3), dtype=torch.float64, device=self.device)
                 out = self.agg_groups
-            elif not torch.is_tensor(out) or out.device != self.device or out.dtype != torch.float64 \
-                    or out.numel() != self.groups * 3 or not out.is_contiguous():
-                raise ValueError(f"aggregate_groups: out must be a contiguous device float64 tensor [{self.groups}][3]")
+            else:
+                L.device_arg(out, "aggregate_groups: out", self.device, torch.float64, numel=self.groups * 3)
             self._call(self.lib.dragg_mpc_aggregate_groups, self._hash(), L.ptr(out), stream=stream)
             return out
 
@@ -606,9 +568,7 @@ class MPCBatch:
             if out is None:
                 out = tuple(torch.empty(s, dtype=d, device=self.device) for s, d in shapes.values())
             for t, (name, (s, d)) in zip(out, shapes.items()):
-                if not torch.is_tensor(t) or t.device != self.device or t.dtype != d or tuple(t.shape) != s \
-                        or not t.is_contiguous():
-                    raise ValueError(f"plan_groups: out's {name} must be a contiguous device tensor {list(s)} of {d}")
+                L.device_arg(t, f"plan_groups: out's {name}", self.device, d, s)
             if src is None:
                 self.drain(stream)
             dims = L.Dims.from_buffer_copy(self.dims)
@@ -667,16 +627,9 @@ class MPCBatch:
         value for every group) and the tensors it points to."""
         G, dev = self.groups, self.device
 
-        def member(x, dtypes, name):
-            if x is None:
-                return None
-            if not torch.is_tensor(x) or x.device != dev or x.dtype not in dtypes or tuple(x.shape) != (G,) \
-                    or not x.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous device tensor [{G}] of {dtypes[0]}, not "
-                                 f"{getattr(x, 'dtype', type(x))} {list(getattr(x, 'shape', []))}")
-            return x
-        keep = (member(seeds, (torch.int64, getattr(torch, "uint64", torch.int64)), "seeds"), member(starts, (torch.int32,), "starts"),
-                member(clocks, (torch.int32,), "clocks"))
+        keep = (None if seeds is None else L.device_arg(seeds, "seeds", dev, SEED_DTYPES, (G,)),
+                None if starts is None else L.device_arg(starts, "starts", dev, torch.int32, (G,)),
+                None if clocks is None else L.device_arg(clocks, "clocks", dev, torch.int32, (G,)))
         return L.Episodes(seed=L.ptr(keep[0]), start_index=L.ptr(keep[1]), timestep=L.ptr(keep[2])), keep
 
     def step_episodes(self, seeds, starts, clocks, noise=None, hist=None, stream=None, t=0):

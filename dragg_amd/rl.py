@@ -178,6 +178,22 @@ def _path_weights(K, weights):
     return w
 
 
+def _env_head(env, va, config, max_poss_load, n_homes):
+    """What the two vector environments' constructors share: the aggregator, its shape and price classes, and the
+    setpoint rule's constants."""
+    from . import inputs as I
+    env.va, env.config = va, config
+    env.E, env.T = va.E, va.num_timesteps
+    # price classes (the aggregator's `price_classes`): actions are then [E][P] or [E][P][n], candidates
+    # [E][C][P] or [E][C][P][n]
+    env.n_classes, env.class_names = getattr(va, "n_classes", 1), getattr(va, "class_names", None)
+    env.prev_timesteps = config["agg"]["rl"]["prev_timesteps"]
+    # (an aggregator with vehicles: each vehicle's max_rate on top of the homes' own loads)
+    env.max_poss_load = (sum(I.max_load(h) for h in va.homes) + getattr(va, "vehicle_max_rate", 0.0)
+                         if max_poss_load is None else max_poss_load)
+    env.n_homes = va.Nb if n_homes is None else int(n_homes)
+
+
 class VectorEnv:
     """E episodes of one community as a vector environment for reward-price policies, on a
     `dragg_amd.vector.VectorAggregator`.
@@ -192,18 +208,7 @@ class VectorEnv:
     the host once per step (the policies are host code)."""
 
     def __init__(self, vector_aggregator, config, max_poss_load=None, n_homes=None):
-        from . import inputs as I
-        self.va = va = vector_aggregator
-        self.config = config
-        self.E, self.T = va.E, va.num_timesteps
-        # price classes (the aggregator's `price_classes`): actions are then [E][P] or [E][P][n], candidates
-        # [E][C][P] or [E][C][P][n]
-        self.n_classes, self.class_names = getattr(va, "n_classes", 1), getattr(va, "class_names", None)
-        self.prev_timesteps = config["agg"]["rl"]["prev_timesteps"]
-        # (an aggregator with vehicles: each vehicle's max_rate on top of the homes' own loads)
-        self.max_poss_load = (sum(I.max_load(h) for h in va.homes) + getattr(va, "vehicle_max_rate", 0.0)
-                              if max_poss_load is None else max_poss_load)
-        self.n_homes = va.Nb if n_homes is None else int(n_homes)
+        _env_head(self, vector_aggregator, config, max_poss_load, n_homes)
         self.timestep = np.zeros(self.E, dtype=np.int64)
         self.parked = np.zeros(self.E, dtype=bool)
         self.agg_load = np.zeros(self.E)
@@ -341,16 +346,8 @@ class DeviceVectorEnv:
 
     def __init__(self, vector_aggregator, config, max_poss_load=None, n_homes=None, plan_keys=(), plan_rows=()):
         from . import _lib as L
-        from . import inputs as I
-        self.va = va = vector_aggregator
-        self.config = config
-        self.E, self.T = va.E, va.num_timesteps
-        self.n_classes, self.class_names = getattr(va, "n_classes", 1), getattr(va, "class_names", None)
-        self.prev_timesteps = config["agg"]["rl"]["prev_timesteps"]
-        # (an aggregator with vehicles: each vehicle's max_rate on top of the homes' own loads)
-        self.max_poss_load = (sum(I.max_load(h) for h in va.homes) + getattr(va, "vehicle_max_rate", 0.0)
-                              if max_poss_load is None else max_poss_load)
-        self.n_homes = va.Nb if n_homes is None else int(n_homes)
+        _env_head(self, vector_aggregator, config, max_poss_load, n_homes)
+        va = self.va
         self.state = va.env_state(self.prev_timesteps, self.max_poss_load, 3 * self.n_homes)
         self.choice = self.scores = None
         self._w = {}

@@ -35,7 +35,10 @@ class-c homes of an episode equal, bit for bit, the same homes of a single run u
 `VectorAggregator(..., vehicles=True)` steps the homes' electric vehicles beside them: an E-group `EVFleet` of its
 own whose groups follow the episodes' start indices, clocks, resets, price rows and price classes
 (dragg_mpc_ev_step_episodes), its three sums added onto the homes' before anything is filed, swept and adopted with
-the homes.  The homes never see the fleet: their rows are those of the same aggregator
+the homes.  The batch and the fleet are one unit here (`members.Members`, DESIGN.md section
+3.15): the live state is one, every sweep's replicas are one, a held first step is a `members.Held`, and each move
+of the state -- prices, step, sums, replicate, adopt, the fleet's reset -- is one call on it, homes first.  The
+homes never see the fleet: their rows are those of the same aggregator
 without vehicles, and every episode's sums and fleet state are a single `DeviceAggregator(ev=...)` run's, bit for bit.
 
 One rank only: sharding episodes over ranks is not built.
@@ -45,6 +48,7 @@ import torch
 
 from . import _lib as L
 from .ev import EVFleet
+from .members import Held, Members
 from .mpc import MPCBatch
 
 
@@ -277,42 +281,6 @@ def resolve_price_classes(price_classes, homes, n_classes=None):
     return cm, P, [str(c) for c in range(P)]
 
 
-class HeldReplicas:
-    """The first step of a K-step sweep, kept while its replica batch moves on: the arrays `MPCBatch.adopt_from`
-    reads (`aggregator.HeldStep`'s), but allocated once and refilled with `copy_` -- an environment step never
-    calls the allocator for them.  The history row is the replica batch's own: only step 0 writes it."""
-    KEYS = ("vals", "fc_store", "status", "iters", "obj", "relax_obj", "int_path")
-
-    def __init__(self, rb):
-        self.N, self.H, self.groups = rb.N, rb.H, getattr(rb, "groups", 1)
-        for k in self.KEYS:
-            v = getattr(rb, k, None)
-            setattr(self, k, torch.empty_like(v) if v is not None else None)
-        # (fc is a view of fc_store where a batch has one: MPCBatch)
-        self.fc = self.fc_store.permute(1, 2, 0) if self.fc_store is not None else torch.empty_like(rb.fc)
-
-    def fill(self, rb):
-        for k in self.KEYS if self.fc_store is not None else self.KEYS + ("fc",):
-            v = getattr(self, k)
-            if v is not None:
-                v.copy_(getattr(rb, k))
-        self.hist_row = getattr(rb, "hist_row", None)
-
-
-class HeldFleet:
-    """`HeldReplicas` for the replica fleet: the arrays `EVFleet.adopt_from` reads, allocated once."""
-    KEYS = ("vals", "fc_store", "status", "obj")
-
-    def __init__(self, rf):
-        self.M, self.H, self.groups = rf.M, rf.H, rf.groups
-        for k in self.KEYS:
-            setattr(self, k, torch.empty_like(getattr(rf, k)))
-
-    def fill(self, rf):
-        for k in self.KEYS:
-            getattr(self, k).copy_(getattr(rf, k))
-
-
 class VectorAggregator:
     def __init__(self, homes, oat, ghi, tou, episodes, seeds, start_indices, num_timesteps, int_mode="round",
                  keep_history=True, device=None, batch_cls=MPCBatch, rank=0, world=1, price_classes=None,
@@ -363,8 +331,11 @@ class VectorAggregator:
         self.status_hist = torch.zeros((T, N), dtype=torch.int32, device=dev)
         self.path_hist = torch.zeros((T, N), dtype=torch.int32, device=dev)
         self.agg_hist = torch.zeros((T, E, 3), dtype=torch.float64, device=dev)
-        self._batch_args = (batch_cls, dict(int_mode=int_mode, device=dev, **batch_kw))
-        self._sweep_batches = {}     # C -> the C * E-group batch of sweep()
+        # the homes and (vehicles=True) their fleet as one unit (members.py): every move of the state goes through it
+        self.members = Members(self.batch, homes=homes,
+                               batch_args=(batch_cls, dict(int_mode=int_mode, device=dev, **batch_kw)),
+                               fleet_args=(fleet_cls, dict(day_offset=int(day_offset), device=dev)),
+                               classes=(self.price_class_host, self.n_classes) if self.n_classes > 1 else None)
         # K-step sweeps: (C, K) -> the sums [K][C * E][3], C -> the held first step, C -> the scores [C * E]
         self._path_sums, self._held, self._path_score = {}, {}, {}
         self.sweep_steps = self.path_scores = None
@@ -373,27 +344,20 @@ class VectorAggregator:
         self._gen = 0
         self.adopted = torch.zeros(E, dtype=torch.bool, device=dev)      # the episodes the last commit advanced
         # the vehicles: fleet_cls is injectable for the same reason batch_cls is (tests/test_ev_vector_host.py)
-        self.fleet = self.ev_sums = self.ev_agg_hist = None
+        self.ev_sums = self.ev_agg_hist = None
         self.vehicle_max_rate = 0.0
-        self._sweep_fleets, self._held_fleets = {}, {}
         if vehicles:
             if not any(h.get("ev") is not None for h in homes):
                 raise ValueError("vehicles=True: no home of the community has an \"ev\" section")
-            self._fleet_args = (fleet_cls, dict(day_offset=int(day_offset), device=dev))
-            self.fleet = self._new_fleet(tou[:self.n_env], E)
+            self.members.fleet = self.members.new_fleet(tou[:self.n_env], E)
             self.ev_sums = self.fleet.sums
             self.vehicle_max_rate = float(sum(float(h["ev"]["max_rate"]) for h in homes if h.get("ev") is not None))
             if keep_history:
                 self.ev_agg_hist = torch.zeros((T, E, 3), dtype=torch.float64, device=dev)
 
-    def _new_fleet(self, tou, groups):
-        """A fleet of `groups` groups of the community's vehicles over `tou` (environment index 0 first), with the
-        owners' price classes."""
-        cls, kw = self._fleet_args
-        f = cls(self.homes, tou, start_index=0, groups=groups, **kw)
-        if self.n_classes > 1:
-            f.set_price_classes([int(self.price_class_host[i]) for i in f.owners], self.n_classes)
-        return f
+    fleet = property(lambda self: self.members.fleet)       # (None: homes only)
+    # C -> the C * E-group replica batch of sweep() (a view of the unit's replicas: drop one there)
+    _sweep_batches = property(lambda self: {k: r.batch for k, r in self.members.replicas.items()})
 
     # ------------------------------------------------------------------ masks and keys
     def _mask(self, mask):
@@ -442,11 +406,7 @@ class VectorAggregator:
         self._set_keys(None if mask is None else m, seeds, start_indices)
         hm = self._homes_mask(m)
         b = self.batch
-        if self.fleet is not None:
-            self.fleet.reset_groups(m.contiguous())
-            if self.ev_agg_hist is not None:
-                self.ev_agg_hist.copy_(torch.where(m[None, :, None], torch.zeros((), dtype=torch.float64,
-                                                                                 device=self.device), self.ev_agg_hist))
+        self._reset_fleet(m)
         nan = torch.full((), float("nan"), dtype=torch.float64, device=self.device)
         self.clocks = torch.where(m, torch.zeros_like(self.clocks), self.clocks)
         self.parked = self.parked & ~m
@@ -457,8 +417,17 @@ class VectorAggregator:
         zero = torch.zeros((), dtype=torch.int32, device=self.device)
         self.status_hist.copy_(torch.where(hm, zero, self.status_hist))
         self.path_hist.copy_(torch.where(hm, zero, self.path_hist))
-        self.agg_hist.copy_(torch.where(m[None, :, None], torch.zeros((), dtype=torch.float64, device=self.device),
-                                        self.agg_hist))
+        self._clear_sums(self.agg_hist, m)
+
+    def _clear_sums(self, store, m):
+        """store[:, e] = 0 for the masked episodes; store [T][E][3]."""
+        store.copy_(torch.where(m[None, :, None], torch.zeros((), dtype=torch.float64, device=self.device), store))
+
+    def _reset_fleet(self, m):
+        """The fleet's part of a reset: the masked groups started over, the vehicles' filed rows cleared."""
+        self.members.reset_fleet(m.contiguous())
+        if self.ev_agg_hist is not None:
+            self._clear_sums(self.ev_agg_hist, m)
 
     def park(self, mask):
         """The masked episodes sit out the coming steps (idle groups: nothing of them is read or written)."""
@@ -484,6 +453,28 @@ class VectorAggregator:
         index = idx.view(1, 1, self.E, 1).expand_as(r)
         s.scatter_(0, index, torch.where(on.view(1, 1, self.E, 1), r, s.gather(0, index)))
 
+    def _scatter_sums(self, store, row, idx, on):
+        """store[idx[e], e] = row[e] for the episodes that are `on`; store [T][E][3], row [E][3]."""
+        ai = idx.view(1, self.E, 1).expand(1, self.E, 3)
+        store.scatter_(0, ai, torch.where(on.view(1, self.E, 1), row.view(1, self.E, 3), store.gather(0, ai)))
+
+    def _ran(self, on):
+        """The clocks the episodes `on` run at, -1 for the others (a tensor of its own)."""
+        return torch.where(on, self.clocks, torch.full_like(self.clocks, -1))
+
+    def _price_rows(self, prices, what, candidates=False):
+        """An action as price rows: `prices` led by [E] (`step`) or [E][C] (`sweep`), then [P] where the community has
+        price classes, then [n] -- or nothing: scalars, so that a 2-D `step` tensor and a 3-D `sweep` tensor mean
+        class scalars when P > 1 -> the float64 device tensor with the [n] axis."""
+        P, nc = L.device_f64(prices, self.device), self.n_classes
+        dims = 2 + bool(candidates) + (nc > 1)
+        if P.dim() == dims - 1:
+            P = P.unsqueeze(-1)
+        if P.dim() != dims or P.shape[0] != self.E or (candidates and P.shape[1] < 1) or (nc > 1 and P.shape[-2] != nc):
+            lead = f"[{self.E}]" + ("[C]" if candidates else "") + (f"[{nc}]" if nc > 1 else "")
+            raise ValueError(f"{what} takes prices {lead} or {lead}[n], not {list(P.shape)}")
+        return P
+
     def step(self, prices, noise=None):
         """One step of every active episode under `prices` ([E], or [E][n] with n == 1 or n >= H: row e is
         episode e's reward-price list); the others stay idle.  -> device tensor [E][3], collect_data's
@@ -494,45 +485,26 @@ class VectorAggregator:
     def _advance(self, prices, noise=None):
         """The solve of `step`: the prices published, every active episode stepped at its own clock (kept in
         `self._keep`, -1 for the others) -> the device bool [E] of the episodes that ran.  Nothing filed yet."""
-        P = L.device_f64(prices, self.device)
-        if self.n_classes > 1:
-            if P.dim() == 2:
-                P = P.unsqueeze(-1)                              # class scalars
-            if P.dim() != 3 or tuple(P.shape[:2]) != (self.E, self.n_classes):
-                raise ValueError(f"step takes class prices [{self.E}][{self.n_classes}] or "
-                                 f"[{self.E}][{self.n_classes}][n], not {list(P.shape)}")
-        else:
-            if P.dim() == 1:
-                P = P.reshape(-1, 1)
-            if P.dim() != 2 or P.shape[0] != self.E:
-                raise ValueError(f"step takes prices [{self.E}] or [{self.E}][n], not {list(P.shape)}")
-        b = self.batch
+        P = self._price_rows(prices, "step")
         self._gen += 1
-        b.set_reward_price(P.contiguous())
+        self.members.set_reward_price(P.contiguous())
         on = self.active()
-        eff = torch.where(on, self.clocks, torch.full_like(self.clocks, -1))
+        eff = self._ran(on)
         if self._row is not None:
             # (a home that hits ERR_MISSING writes no history: its row entries stay NaN, as in a single run's
             # fresh history row)
             self._row.fill_(float("nan"))
-        b.step_episodes(self.seeds, self.starts, eff, noise=noise, hist=self._row)
-        if self.fleet is not None:           # after the homes, on the same stream, with the same keys and rows
-            self.fleet.set_reward_price(P.contiguous())
-            self.fleet.step_episodes(self.starts, eff)
+        # (the fleet after the homes, on the same stream, with the same keys and rows)
+        self.members.step_episodes(self.seeds, self.starts, eff, noise=noise, hist=self._row)
         self._keep = eff
         return on
 
-    def _sums(self, on=None, idx=None):
+    def _sums(self, on, idx):
         """The live state's sums [E][3]: the homes', plus the vehicles' where there is a fleet (whose own rows are
         then filed for the episodes `on` at the rows `idx`)."""
-        agg = self.batch.aggregate_groups()
-        if self.fleet is None:
-            return agg
-        agg = self.fleet.aggregate_onto(agg)
-        if self.ev_agg_hist is not None and on is not None:
-            a = self.ev_agg_hist
-            ai = idx.view(1, self.E, 1).expand(1, self.E, 3)
-            a.scatter_(0, ai, torch.where(on.view(1, self.E, 1), self.fleet.sums.view(1, self.E, 3), a.gather(0, ai)))
+        agg = self.members.sums()
+        if self.ev_agg_hist is not None:
+            self._scatter_sums(self.ev_agg_hist, self.fleet.sums, idx, on)
         return agg
 
     def _file(self, on):
@@ -546,9 +518,7 @@ class VectorAggregator:
         self._scatter(self.status_hist, b.status, idx, on)
         if hasattr(b, "int_path"):
             self._scatter(self.path_hist, b.int_path, idx, on)
-        a = self.agg_hist                                        # [T][E][3]
-        ai = idx.view(1, self.E, 1).expand(1, self.E, 3)
-        a.scatter_(0, ai, torch.where(on.view(1, self.E, 1), agg.view(1, self.E, 3), a.gather(0, ai)))
+        self._scatter_sums(self.agg_hist, agg, idx, on)
         self.clocks = self.clocks + on.to(torch.int32)
         return agg
 
@@ -558,23 +528,6 @@ class VectorAggregator:
     # dragg_mpc_replicate and stepped (K times) with the episodes' keys and clocks tiled C times.  `commit` then
     # adopts, per episode, the chosen copy's solved first step (dragg_mpc_adopt) instead of solving it again;
     # the choice can be made on the device (`select`, `select_paths`), so none of this synchronises with the host.
-    def _sweep_batch(self, C):
-        rb = self._sweep_batches.get(C)
-        if rb is None:
-            cls, kw = self._batch_args
-            rb = cls(self.homes, None, None, None, 0, (0.0,), groups=C * self.E, **kw)
-            if self.n_classes > 1:
-                rb.set_price_classes(self.price_class_host, self.n_classes)       # the same map
-            self._sweep_batches[C] = rb
-            if self.fleet is not None:       # the replica fleet: the live one's environment, C * E groups
-                self._sweep_fleets[C] = self._new_fleet(self.fleet.tou, C * self.E)
-        for k in ("oat", "ghi", "tou", "start_index"):           # the live batch's environment (the same tensors)
-            if hasattr(self.batch, k):
-                setattr(rb, k, getattr(self.batch, k))
-        if hasattr(self.batch, "dims"):
-            rb.dims.n_env = self.batch.dims.n_env
-        return rb
-
     def sweep(self, prices, steps=1, hold=True):
         """Every active episode's next step under each of its C candidate prices (`prices` [E][C], or
         [E][C][n] with n == 1 or n >= H), nothing committed -> device tensor [E][C][3], row (e, c)
@@ -595,82 +548,52 @@ class VectorAggregator:
         K = int(steps)
         if K < 1:
             raise ValueError(f"sweep takes steps >= 1, not {steps!r}")
-        P = L.device_f64(prices, self.device)
-        nc = self.n_classes
-        if nc > 1:
-            if P.dim() == 3:
-                P = P.unsqueeze(-1)                              # class scalars
-            if P.dim() != 4 or P.shape[0] != self.E or P.shape[1] < 1 or P.shape[2] != nc:
-                raise ValueError(f"sweep takes class prices [{self.E}][C][{nc}] or [{self.E}][C][{nc}][n], not "
-                                 f"{list(P.shape)}")
-        else:
-            if P.dim() == 2:
-                P = P.unsqueeze(-1)
-            if P.dim() != 3 or P.shape[0] != self.E or P.shape[1] < 1:
-                raise ValueError(f"sweep takes prices [{self.E}][C] or [{self.E}][C][n], not {list(P.shape)}")
+        P, nc = self._price_rows(prices, "sweep", candidates=True), self.n_classes
         C = int(P.shape[1])
         Pc = P.transpose(0, 1).contiguous()                      # copy-major: [C][E][n] ([C][E][P][n] with classes)
         self._hold = None
-        rb = self._sweep_batch(C)
-        rb.set_reward_price(Pc.view(C * self.E, nc, -1) if nc > 1 else Pc.view(C * self.E, -1))
-        rb.replicate_from(self.batch)
+        r = self.members.replica(C * self.E, key=C)
+        r.set_reward_price(Pc.view(C * self.E, nc, -1) if nc > 1 else Pc.view(C * self.E, -1))
+        r.replicate_from(self.members)
         on = self.active()
-        eff = torch.where(on, self.clocks, torch.full_like(self.clocks, -1))
+        eff = self._ran(on)
+        rb = r.batch
         if hold and self._row is not None:
             if getattr(rb, "hist_row", None) is None:
                 rb.hist_row = torch.empty((L.NVAL, rb.N), dtype=torch.float64, device=self.device)
             rb.hist_row.fill_(float("nan"))
         keys = (self.seeds.repeat(C), self.starts.repeat(C), eff.repeat(C))
-        rb.step_episodes(*keys, hist=rb.hist_row if hold and self._row is not None else None)
-        rf = self._sweep_fleets.get(C)
-        if rf is not None:                   # the replica fleet: the same rows, copies and tiled keys
-            rf.set_reward_price(Pc.view(C * self.E, nc, -1) if nc > 1 else Pc.view(C * self.E, -1))
-            rf.replicate_from(self.fleet)
-            rf.step_episodes(keys[1], keys[2])
+        r.step_episodes(*keys, hist=rb.hist_row if hold and self._row is not None else None)
+        # (a hold's "unit" is what `commit` adopts from -- the replicas, or the held copy of their first step --
+        # and "src" its homes' half)
+        hold = {"C": C, "P": Pc, "gen": self._gen, "on": on, "unit": r, "src": rb, "keys": keys} if hold else None
         if K > 1:
-            return self._roll(rb, C, K, Pc, on, eff, keys, hold)
-        sums = rb.aggregate_groups()
-        if rf is not None:
-            sums = rf.aggregate_onto(sums)
-        sums = sums.view(C, self.E, 3)
-        if hold:
-            self._hold = {"C": C, "P": Pc, "gen": self._gen, "on": on, "src": rb, "keys": keys, "fleet": rf}
-        return sums.permute(1, 0, 2).contiguous()
+            return self._roll(r, C, K, eff, keys, hold)
+        self._hold = hold
+        return r.sums().view(C, self.E, 3).permute(1, 0, 2).contiguous()
 
-    def _roll(self, rb, C, K, Pc, on, eff, keys, hold):
-        """The rest of a K-step sweep after the replicas' step 0: its sums, the held copy of it, then steps
-        1 .. K - 1 of the replicas, each step's sums written in place into block j of the [K][C * E][3] buffer
-        kept per (C, K).  The clock rows are fixed-shape ops: no host synchronisation."""
+    def _roll(self, r, C, K, eff, keys, hold):
+        """The rest of a K-step sweep after the replicas' step 0: its sums, the held copy of it (`hold`: the hold
+        that will keep it, or None), then steps 1 .. K - 1 of the replicas, each step's sums written in place into
+        block j of the [K][C * E][3] buffer kept per (C, K).  The clock rows are fixed-shape ops: no host
+        synchronisation."""
         E, T = self.E, self.num_timesteps
         buf = self._path_sums.get((C, K))
         if buf is None:
             buf = self._path_sums[(C, K)] = torch.zeros((K, C * E, 3), dtype=torch.float64, device=self.device)
-        rb.aggregate_groups(out=buf[0])
-        rf = fsrc = self._sweep_fleets.get(C)
-        if rf is not None:
-            rf.aggregate_onto(buf[0])
-        src = rb
-        if hold:
-            src = self._held.get(C)
-            if src is None:
-                src = self._held[C] = HeldReplicas(rb)
-            src.fill(rb)
-            if rf is not None:
-                fsrc = self._held_fleets.get(C)
-                if fsrc is None:
-                    fsrc = self._held_fleets[C] = HeldFleet(rf)
-                fsrc.fill(rf)
+        r.sums(out=buf[0])
+        if hold is not None:
+            held = self._held.get(C)
+            if held is None:
+                held = self._held[C] = Held(r)
+            hold["unit"] = hold["src"] = held.fill(r, getattr(r.batch, "hist_row", None))
         idle = torch.full_like(eff, -1)
         for j in range(1, K):
             clk = torch.where((eff >= 0) & (eff + j < T), eff + j, idle).repeat(C)
-            rb.step_episodes(keys[0], keys[1], clk)
-            rb.aggregate_groups(out=buf[j])
-            if rf is not None:
-                rf.step_episodes(keys[1], clk)
-                rf.aggregate_onto(buf[j])
+            r.step_episodes(keys[0], keys[1], clk)
+            r.sums(out=buf[j])
         self.sweep_steps = torch.where(eff >= 0, (T - eff).clamp(max=K), torch.zeros_like(eff))
-        if hold:
-            self._hold = {"C": C, "P": Pc, "gen": self._gen, "on": on, "src": src, "keys": keys, "fleet": fsrc}
+        self._hold = hold
         out = buf.view(K, C, E, 3).permute(2, 1, 0, 3).contiguous()
         self._paths = (out, buf)
         return out
@@ -699,7 +622,7 @@ class VectorAggregator:
         if score is None:
             score = self._path_score[C] = torch.full((C * E,), float("nan"), dtype=torch.float64, device=dev)
         on = self.active()
-        ran = torch.where(on, self.clocks, torch.full_like(self.clocks, -1))
+        ran = self._ran(on)
         choice = self.batch.select_paths(sums, ran, L.device_f64(tracked, dev).reshape(E, -1).contiguous(),
                                          L.device_f64(setpoints, dev).reshape(-1).contiguous(), w, P,
                                          self.num_timesteps, 0.5 * float(max_poss_load), score=score)
@@ -749,7 +672,7 @@ class VectorAggregator:
         h = self._hold
         if h is None or h["gen"] != self._gen:
             raise ValueError("commit: no sweep of the live state is held (sweep first; a step or a reset voids it)")
-        C, rb, b = h["C"], h["src"], self.batch
+        C = h["C"]
         if not torch.is_tensor(choice) or tuple(choice.shape) != (self.E,) or choice.dtype.is_floating_point:
             raise ValueError(f"commit takes a device int tensor [{self.E}]")
         self._hold = None
@@ -758,13 +681,10 @@ class VectorAggregator:
         ch = torch.where(on, ch, torch.full_like(ch, -1)).contiguous()
         self._gen += 1
         rows = h["P"][ch.clamp(0, C - 1).to(torch.int64), torch.arange(self.E, device=self.device)]
-        b.set_reward_price(rows.contiguous())
+        self.members.set_reward_price(rows.contiguous())
         if self._row is not None:
             self._row.fill_(float("nan"))
-        b.adopt_from(rb, ch, hist=self._row)
-        if self.fleet is not None:
-            self.fleet.set_reward_price(rows.contiguous())
-            self.fleet.adopt_from(h["fleet"], ch)
+        self.members.adopt_from(h["unit"], ch, hist=self._row)
         self.adopted = on
         return on
 
@@ -779,7 +699,7 @@ class VectorAggregator:
         """File the step of the episodes `on`; `ran`: the clocks they ran at, -1 for the others (a tensor of
         its own: the kernel reads it in every block and writes the clocks)."""
         if ran is None:
-            ran = torch.where(on, self.clocks, torch.full_like(self.clocks, -1))
+            ran = self._ran(on)
         agg = self._sums(on, ran.clamp(0, self.num_timesteps - 1).to(torch.int64))
         self.batch.env_file(st, ran, agg, hist=self._row)
         return agg
@@ -814,11 +734,7 @@ class VectorAggregator:
         self._set_keys(None if mask is None else m, host.get("seeds"), host.get("start_indices"))
         self.parked = self.parked & ~m
         self.batch.env_reset(st, m.contiguous())
-        if self.fleet is not None:
-            self.fleet.reset_groups(m.contiguous())
-            if self.ev_agg_hist is not None:
-                self.ev_agg_hist.copy_(torch.where(m[None, :, None], torch.zeros((), dtype=torch.float64,
-                                                                                 device=self.device), self.ev_agg_hist))
+        self._reset_fleet(m)
 
     # ------------------------------------------------------------------ plan observations
     def plan(self, keys, rows=(), out=None, classes=False):

@@ -254,8 +254,9 @@ def community20():
 
 @pytest.mark.parametrize("steps", [1, 2])
 def test_sweep_plan_of_a_held_sweep(gpu, community20, steps):
-    """G = 3 candidates against 20 homes after two committed steps; steps = 2 holds a `HeldStep`."""
-    from dragg_amd.aggregator import DeviceAggregator, HeldStep
+    """G = 3 candidates against 20 homes after two committed steps; steps = 2 holds a `Held`."""
+    from dragg_amd.aggregator import DeviceAggregator
+    from dragg_amd.members import Held
     from dragg_amd.vector import plan_groups_reference
     homes, (oat, ghi, tou) = community20
     agg = DeviceAggregator(homes, oat, ghi, tou, 0, 8, reward_price=[0.0] * 24, seed=5)
@@ -268,7 +269,7 @@ def test_sweep_plan_of_a_held_sweep(gpu, community20, steps):
     P = np.stack([np.full(24, 0.05), np.full(24, -0.03), -0.03 * np.cos(np.arange(24))])
     sums = agg.sweep(P, steps, hold=True)
     src = agg._hold["src"]
-    assert isinstance(src, HeldStep) == (steps == 2)
+    assert isinstance(src, Held) == (steps == 2)
     curve, count, stats = (x.clone() for x in agg.sweep_plan(keys, ROWS4))
     torch.cuda.synchronize()
     H = agg.batch.H

@@ -323,7 +323,7 @@ def test_sweep_plan_raises_without_a_hold():
     agg.sweep(PRICES, 1)                                             # (not held)
     with pytest.raises(ValueError, match="held"):
         agg.sweep_plan(("p_grid",))
-    for steps in (1, 2):                                             # the replica batch itself / a HeldStep
+    for steps in (1, 2):                                             # the replica batch itself / a Held
         agg.sweep(PRICES, steps, hold=True)
         src = agg._hold["src"]
         assert (src is agg._sweep_batches[3]) == (steps == 1)

@@ -62,7 +62,8 @@ def main():
         raise SystemExit("commit_bench.py: no GPU (a timing needs one)")
     import bench
     from dragg_amd import _lib as L
-    from dragg_amd.aggregator import DeviceAggregator, HeldStep
+    from dragg_amd.aggregator import DeviceAggregator
+    from dragg_amd.members import Held
     from dragg_amd.community import reference_completable, synthetic_homes, synthetic_weather
     from dragg_amd.vector import VectorAggregator
 
@@ -168,11 +169,12 @@ def main():
                 ta2, tb2 = rotate(lambda: today(fh), lambda: held(fh), reset, max(2, args.reps // 2))
                 reset()
                 agg.sweep(P, 1, hold=True)
+                unit = agg._hold["unit"]
                 row[f"steps{fh}"] = {"today_ms": stats(ta2), "held_ms": stats(tb2),
-                                     "clone_ms": round(kernel_time(lambda i: HeldStep(rb, rb.hist_row), 5), 4)}
+                                     "clone_ms": round(kernel_time(lambda i: Held(unit).fill(unit, rb.hist_row), 5), 4)}
             rows.append(row)
             reset()
-            del agg._sweep_batches[G]
+            del agg.members.replicas[G]
             agg._hold = None
             torch.cuda.empty_cache()
         line["rl"] = {"config": {"homes": len(homes), "horizon": H, "dt": args.dt, "month": args.month,
